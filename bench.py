@@ -15,13 +15,19 @@ One STEP = the system's ingest+search cycle on every rank (one process per GPU):
      --opt index_prune=none runs that full bf16 scan).
 So every step embeds 256*N sentences AND answers 256*N top-10 queries over the full 100M-row
 corpus: value = embeds/s = top-k QPS (whole job).  Per-rank work is constant in N ("weak").
-After the timed steps the same line also reports the held-out search rate (heldout_topk_qps:
-fresh queries drawn from the corpus distribution, never inserted, on the same shard).
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what
+takes runs of its own: after the timed steps the same line also reports the held-out search rate
+(heldout_topk_qps: fresh queries drawn from the corpus distribution, never inserted, on the same
+shard).  --dump-outputs DIR writes what the last timed step computed (the embeddings of the
+batch it searched and that batch's top-k scores and ids; --mode embed / search: their half) as
+DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
 
 Data: synthetic token ids, random-init weights (real MiniLM-L6 architecture), random unit
 index rows -- there is no network for checkpoints or datasets.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--opt KEY=VALUE ...]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                       [--opt KEY=VALUE ...]
        N > 1 either under a launcher (python -m torch.distributed.run --nproc-per-node N ...
        bench.py --gpus N: WORLD_SIZE is set) or plainly: with WORLD_SIZE unset this process
        launches the N ranks itself as fresh child processes BEFORE touching the GPU (one per GPU,
@@ -129,9 +135,10 @@ OPTS = {
     "simulate_world": (0, int, "PROJECTION on one GPU: the per-rank work of the N-GPU step (a "
                                "100M/N shard, 256*N gathered queries); the JSON says SIMULATED"),
     "timeline": ("", str, "write per-step GPU times (+ sampled clock/power) to this JSONL file"),
-    "heldout_searches": (20, int, "--mode full: after the timed steps, time this many searches of "
-                                  "fresh held-out queries (drawn from the corpus distribution, "
-                                  "never inserted) on the same shard: heldout_topk_qps"),
+    "heldout_searches": (20, int, "--full, --mode full: after the timed steps, time this many "
+                                  "searches of fresh held-out queries (drawn from the corpus "
+                                  "distribution, never inserted) on the same shard: "
+                                  "heldout_topk_qps"),
     "index_prefilter": ("none", str, "none | fp8 (e4m3 copy for 3k candidates + exact bf16 "
                                      "rescore; Qdrant quantization + rescore)"),
     "index_prune": ("i8", str, "i8 (EXACT pruned search: int8 / MX-fp4 stream scan of a "
@@ -166,6 +173,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that take runs of their own after the timed "
+                         "steps (the held-out search rate, --opt heldout_searches); a plain run "
+                         "only sets up, warms up, times the steps and reports")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as "
+                         "DIR/<name>.npy (float32 / float64; rank r > 0 writes <name>.rank<r>.npy)")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--seq", type=int, default=128)
     ap.add_argument("--index-rows", type=int, default=100_000_000)
@@ -205,6 +219,8 @@ def parse_args(argv=None):
         ap.error("--opt index_prefilter: none | fp8; index_prune: i8 | none")
     if opts["encode_ahead"] not in (1, 2):
         ap.error("--opt encode_ahead: 1 | 2")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps >= 1, --warmup >= 0")
     args.opts_changed = {k: v for k, v in opts.items() if v != OPTS[k][0]}
     for k, v in opts.items():
         setattr(args, k, v)
@@ -300,6 +316,48 @@ def _claim_stdout() -> None:
 
 def _emit_result(line: str) -> None:
     print(line, file=_RESULT_OUT or sys.stdout, flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files of one rank together
+
+
+def dump_outputs(args, info, arrays: dict) -> None:
+    """--dump-outputs DIR: what the last timed step computed, one DIR/<name>.npy per array
+    (float dtypes as float32, integer ids as float64: exact below 2^53).  An output over its
+    share of the 64 MB is cut to a fixed, seeded sample of its rows."""
+    if not arrays:
+        return
+    import numpy as np
+
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    budget = DUMP_MAX_BYTES // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.to(torch.float32 if t.is_floating_point() else torch.float64)
+        a = t.cpu().numpy()
+        if a.nbytes > budget:
+            rows = max(1, budget // max(1, a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))]
+        suffix = "" if info.rank == 0 else f".rank{info.rank}"
+        np.save(os.path.join(args.dump_outputs, f"{name}{suffix}.npy"), a)
+
+
+def _step_arrays(args, emb, unit, res) -> dict:
+    """The arrays a caller of one step receives: the batch's pooled and unit embeddings
+    (--mode full / embed) and its top-k scores and global ids (--mode full / search)."""
+    arrays = {}
+    if args.mode != "search":
+        arrays.update(embeddings=emb, unit_embeddings=unit)
+    if args.mode != "embed":
+        # rows that tie EXACTLY in score come out of the GPU search in either order from run to
+        # run (candidates are appended atomically): listed by ascending id here, so that two
+        # runs' files compare equal
+        s, g = res
+        by_id = torch.argsort(g, dim=1, stable=True)
+        s, g = s.gather(1, by_id), g.gather(1, by_id)
+        by_score = torch.argsort(s, dim=1, descending=True, stable=True)
+        arrays.update(topk_scores=s.gather(1, by_score), topk_ids=g.gather(1, by_score))
+    return arrays
 
 
 def metric_and_config(args, info, cfg, prune, prefilter, extra_cfg: dict):
@@ -463,30 +521,34 @@ def run_cpu(args, info, comm) -> int:
     qsets = [gen.unit(B, 5000 + 10 * info.rank + i).bfloat16() for i in range(4)]
 
     def step(i):
-        q = None
+        emb = res = None
         if args.mode != "search":
-            _, q = enc.forward_packed(host[i % 4])
+            emb, q = enc.forward_packed(host[i % 4])
             if args.queries == "self":
                 shard.append_unit(q)
         else:
             q = qsets[i % 4] if args.queries == "heldout" else shard.rows[(i * B) % max(1, shard.count - B):][:B]
         if args.mode != "embed":
-            searcher.search(q, args.k)
+            res = searcher.search(q, args.k)
         if args.mode != "search" and args.queries == "heldout":
             shard.append_unit(q)
+        return emb, q, res
 
     for i in range(W):
         step(i)
     D.barrier(info)
     t0 = time.perf_counter()
     for j in range(K):
-        step(W + j)
+        last = step(W + j)
     D.barrier(info)
     elapsed = D.allreduce_max(info, time.perf_counter() - t0)
     ms = elapsed * 1000.0 / K
     total = B * info.world * K / elapsed
+    if args.dump_outputs:
+        dump_outputs(args, info, _step_arrays(args, *last))
     extra = {}
-    if args.mode == "full" and args.heldout_searches > 0:   # (the GPU run's held-out phase)
+    # (the GPU run's held-out phase)
+    if args.full and args.mode == "full" and args.heldout_searches > 0:
         H = args.heldout_searches
         hq = [gen.unit(B, 9000 + 10 * info.rank + i).bfloat16() for i in range(2)]
         D.barrier(info)
@@ -576,6 +638,8 @@ def run_embed(args, info, comm, enc, cfg, t_setup: float) -> int:
     elapsed = D.allreduce_max(info, time.perf_counter() - t_start)
     ms = elapsed * 1000.0 / K
     total = B * info.world * K / elapsed
+    if args.dump_outputs:   # the last replay's
+        dump_outputs(args, info, _step_arrays(args, out32, outu, None))
     extra_out = {
         "embed_ms_per_step_rank0": round(sum(a.elapsed_time(b) for a, b in evs) / K, 3),
         "host_enqueue_ms_per_step_rank0": round(host_ms, 3),
@@ -791,7 +855,7 @@ def run_gpu(args, info, comm) -> int:
             handles[i] = searcher.begin(q, args.k)
             pre_done[slot].record(pre_stream)
 
-    def step_pipelined(i: int, ev=None) -> None:
+    def step_pipelined(i: int, ev=None):
         slot = i % NO
         # with AHEAD = 2, batch i + 2's encoder is enqueued now: it runs once batch i's scan
         # releases the CUs, beside batch i + 1's pre-pass, instead of between them
@@ -807,7 +871,7 @@ def run_gpu(args, info, comm) -> int:
             compute.wait_event(enc_done[(i + 1) % NO])
         if ev:
             ev[2].record(compute)
-        searcher.end(handles.pop(i))
+        res = searcher.end(handles.pop(i))
         hph["enc_enqueue"] += t1 - t0      # (includes prefetch: its waits / tokens counted too)
         hph["search_begin_enqueue"] += t2 - t1
         hph["search_end_enqueue"] += time.perf_counter() - t2
@@ -815,8 +879,9 @@ def run_gpu(args, info, comm) -> int:
         q_free[slot].record(compute)
         if ev:
             ev[3].record(compute)
+        return res
 
-    def step_overlap(i: int, ev=None) -> None:
+    def step_overlap(i: int, ev=None):
         """Search batch i (encoded by the previous step) while batch i+1 encodes."""
         if pipeline:
             return step_pipelined(i, ev)
@@ -828,24 +893,28 @@ def run_gpu(args, info, comm) -> int:
         q = outs[slot][1]
         if args.queries == "self":
             shard.append_unit(q)
-        searcher.search(q, args.k)
+        res = searcher.search(q, args.k)
         if args.queries == "heldout":
             shard.append_unit(q)
         out_ring.consume(slot)
         q_free[slot].record(compute)
         if ev:
             ev[3].record(compute)
+        return res
 
-    def step(i: int, ev=None) -> None:
+    def step(i: int, ev=None):
+        """One step; returns what it computed last: the search's (scores, ids), or in embed
+        mode the group's pooled embeddings (rank 0) / None."""
         if overlap:
             return step_overlap(i, ev)
         slot = i % 2
+        res = None
         if ev:
             ev[0].record(compute)
         if group_dp:
             if info.is_root:
                 compute.wait_event(copy_done[slot])
-                egroup.embed(dbuf[slot], cu_host=host[i % NB].cu_seqlens)
+                res = egroup.embed(dbuf[slot], cu_host=host[i % NB].cu_seqlens)
                 consumed[slot].record(compute)
                 prefetch(i + 1)
             else:
@@ -865,11 +934,12 @@ def run_gpu(args, info, comm) -> int:
             ev[1].record(compute)
             ev[2].record(compute)
         if args.mode != "embed":
-            searcher.search(q, args.k)
+            res = searcher.search(q, args.k)
         if args.mode == "full" and args.queries == "heldout":
             shard.append_unit(q)
         if ev:
             ev[3].record(compute)
+        return res
 
     prefetch(0)
     if overlap:
@@ -893,7 +963,7 @@ def run_gpu(args, info, comm) -> int:
     evs = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(K)]
     t_start = time.perf_counter()
     for j in range(K):
-        step(W + j, evs[j])
+        last = step(W + j, evs[j])
     host_ms = (time.perf_counter() - t_start) * 1000.0 / K   # host enqueue time per step
     torch.cuda.synchronize(dev)
     D.barrier(info)
@@ -947,7 +1017,16 @@ def run_gpu(args, info, comm) -> int:
                                            else round(shard.calib_share, 3))
         print(f"[bench] rank {info.rank} searches: {ovf} overflowed, max "
               f"{int(shard._mq_tot[1].item())} candidates per query", file=sys.stderr, flush=True)
-    if args.mode == "full" and args.heldout_searches > 0:
+    if args.dump_outputs:
+        # the last timed step's batch: its embeddings are still in its output slot (the encoder
+        # runs at most NO - 1 batches ahead of the search)
+        if group_dp:
+            arrays = {} if last is None else {"embeddings": last}
+        else:
+            e32, eu = outs[(W + K - 1) % NO] if overlap else (out_f32, out_unit)
+            arrays = _step_arrays(args, e32, eu, last)
+        dump_outputs(args, info, arrays)
+    if args.full and args.mode == "full" and args.heldout_searches > 0:
         # the realistic search rate beside the headline: fresh held-out queries (drawn from the
         # corpus distribution, never inserted -- the reference serves arbitrary user text,
         # api_service/src/main.rs:272-512) searched on the same shard after the timed steps

@@ -8,13 +8,13 @@ Configs (BASELINE.md "Measured" table):
   2 minilm-embed    all-MiniLM-L6-v2 bf16 embedding, batch 256      bench.py --mode embed
   3 index-100m      100M x 384 sharded cosine top-10                bench.py --mode search
   4 bge-dp          bge-base-en-v1.5 DP embedding over RCCL         bench.py --model bge-base --mode embed --opt embed_dp=group
-  5 e5-fp8          e5-large-v2 + fp8 index (1B rows at N >= 4)     bench.py --model e5-large --index-dtype fp8
-  + headline        MiniLM embed + top-10 over 100M x 384           bench.py
+  5 e5-fp8          e5-large-v2 + fp8 index (1B rows at N >= 4)     bench.py --full --model e5-large --index-dtype fp8
+  + headline        MiniLM embed + top-10 over 100M x 384           bench.py --full
   + mpnet-embed     the reference's own model (paraphrase-multilingual-mpnet-base-v2, 768-d)
                     bf16 embedding, batch 256                       bench.py --model mpnet-multi --mode embed
   + mpnet-full      the reference's default deployment: mpnet embed + top-10 over a
                     100M x 768 collection (vector_memory_service/src/main.rs:22)
-                                                                    bench.py --model mpnet-multi
+                                                                    bench.py --full --model mpnet-multi
   + e5-embed        e5-large-v2 bf16 embedding (every projection on our kernels)
 Each config runs as a CHILD process (torch.distributed.run for N > 1) under its own timeout.
 """
@@ -69,11 +69,12 @@ def main():
         # N > 1: one global batch per step split over the GPUs and gathered back over RCCL
         ("bge-dp", launch + common + ["--model", "bge-base", "--mode", "embed",
                                       "--opt", "embed_dp=group"], 600),
-        ("e5-fp8", launch + common + ["--model", "e5-large", "--index-dtype", "fp8",
+        ("e5-fp8", launch + common + ["--full", "--model", "e5-large", "--index-dtype", "fp8",
                                       "--encoder-dtype", "fp8", "--index-rows", str(fp8_rows)], 1200),
-        ("headline", launch + common, 900),
+        # --full: the held-out search rate rides in the full-step configs' lines
+        ("headline", launch + common + ["--full"], 900),
         ("mpnet-embed", launch + common + ["--model", "mpnet-multi", "--mode", "embed"], 600),
-        ("mpnet-full", launch + common + ["--model", "mpnet-multi"], 1200),
+        ("mpnet-full", launch + common + ["--full", "--model", "mpnet-multi"], 1200),
         ("e5-embed", launch + common + ["--model", "e5-large", "--mode", "embed"], 600),
     ]
     only = set(filter(None, a.only.split(",")))

@@ -25,7 +25,7 @@ def _run(args, env_extra=None, drop=("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER
 
 
 def test_bench_self_launches_n_ranks():
-    p, out = _run(["--gpus", "2"] + TINY)
+    p, out = _run(["--gpus", "2", "--full"] + TINY)
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(out) == 1, p.stdout          # exactly one JSON line, from rank 0 ...
     assert p.stdout.strip().splitlines() == [json.dumps(out[0])], p.stdout   # ... and nothing else
@@ -34,8 +34,40 @@ def test_bench_self_launches_n_ranks():
     assert r["comm_check"]["collective"].startswith("all_gather ok")
     assert r["config"]["global_batch"] == 8 and r["config"]["parallelism"] == "dp2+index_shard2"
     assert r["value"] > 0 and r["steps"] == 2 and r["warmup"] == 1
-    # the realistic (held-out query) search rate rides in the same line
+    # --full: the realistic (held-out query) search rate rides in the same line
     assert r["heldout_searches"] == 3 and r["heldout_topk_qps"] > 0 and r["heldout_ms_per_search"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full the run times its steps and nothing more (no held-out phase), --steps sets
+    the number of timed steps, and --dump-outputs writes the last step's arrays as float .npy
+    files that a second run with the same arguments reproduces exactly."""
+    import numpy as np
+
+    runs = []
+    for name in ("a", "b"):
+        p, out = _run(["--gpus", "1", "--dump-outputs", str(tmp_path / name)] + TINY)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert len(out) == 1, p.stdout
+        runs.append(out[0])
+    r = runs[0]
+    assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0
+    assert abs(r["value"] - 4 * 1000.0 / r["ms_per_step"]) / r["value"] < 0.01
+    assert not [k for k in r if k.startswith("heldout_")]
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == ["embeddings.npy", "topk_ids.npy", "topk_scores.npy", "unit_embeddings.npy"]
+    shapes = {"embeddings.npy": (4, 384), "unit_embeddings.npy": (4, 384),
+              "topk_scores.npy": (4, 10), "topk_ids.npy": (4, 10)}
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == shapes[n], (n, a.dtype, a.shape)
+        assert np.isfinite(a).all() and np.array_equal(a, b), n
+    # self queries are upserted before they are searched: every best score is the query's own
+    # row's (or a near-duplicate's), 1 up to the bf16 rounding of the stored unit rows; the ids
+    # name rows of the shard (6000 corpus rows + 3 steps of 4)
+    s, ids = np.load(tmp_path / "a" / "topk_scores.npy"), np.load(tmp_path / "a" / "topk_ids.npy")
+    assert np.abs(s[:, 0] - 1.0).max() < 2.0 ** -6 and (np.diff(s, axis=1) <= 0).all()
+    assert (ids == np.floor(ids)).all() and ids.min() >= 0 and ids.max() < 6012
 
 
 def test_bench_world_mismatch_fails():
@@ -76,13 +108,15 @@ def test_bench_search_clustered_heldout_two_ranks():
 
 def test_bench_help_lists_at_most_15_options():
     """The headline's knobs stay few (VERDICT r4 housekeeping): the secondary ones live under
-    --opt KEY=VALUE and an unknown key fails loudly."""
+    --opt KEY=VALUE and an unknown key fails loudly.  The two switches of the driver contract,
+    --full and --dump-outputs, configure no workload and are not counted among the 15."""
     p = subprocess.run([sys.executable, "bench.py", "--help"], cwd=ROOT, capture_output=True,
                        text=True, timeout=120)
     assert p.returncode == 0
     opts = {ln.split()[0].rstrip(",") for ln in p.stdout.splitlines()
             if ln.startswith("  -") and not ln.startswith("  -h")}
-    assert len(opts) <= 15, sorted(opts)
+    assert {"--full", "--dump-outputs"} <= opts, sorted(opts)
+    assert len(opts - {"--full", "--dump-outputs"}) <= 15, sorted(opts)
     bad = subprocess.run([sys.executable, "bench.py", "--opt", "nope=1"], cwd=ROOT,
                          capture_output=True, text=True, timeout=120)
     assert bad.returncode != 0 and "expected KEY=VALUE" in bad.stderr

@@ -228,38 +228,50 @@ async def _script_output(Broker, script):
     outs = [bytearray() for _ in conns]
     closed: set[int] = set()
 
-    async def sync():
+    async def read_to_pong(i):
+        r = conns[i][0]
+        while True:
+            line = await asyncio.wait_for(r.readline(), 5)
+            if line == b"PONG\r\n":
+                return
+            outs[i] += line
+            if not line:          # the server closed this connection (protocol error)
+                closed.add(i)
+                return
+            if line.startswith((b"MSG ", b"HMSG ")):
+                # a message body is framed by the byte count that ends its line, not by lines:
+                # a payload may itself hold b"PONG\r\n"
+                outs[i] += await asyncio.wait_for(r.readexactly(int(line.split()[-1]) + 2), 5)
+
+    async def sync(c, data):
         # a PING/PONG round trip on EVERY connection after each op makes the outputs
-        # deterministic (the broker handles one connection's bytes in order)
-        for i, (r, w) in enumerate(conns):
-            if i in closed:
-                continue
-            w.write(b"PING\r\n")
-            while True:
-                line = await asyncio.wait_for(r.readline(), 5)
-                if line == b"PONG\r\n":
-                    break
-                outs[i] += line
-                if not line:          # the server closed this connection (protocol error)
-                    closed.add(i)
-                    break
+        # deterministic (the broker handles one connection's bytes in order).  The op and its
+        # connection's PING leave in ONE write: a server that answers the op by closing the
+        # connection has then read all that was sent (a PING that arrives after the close is
+        # answered with a reset, which the client may see before it has read the -ERR line)
+        conns[c][1].write(data + b"PING\r\n")
+        for i, (_, w) in enumerate(conns):
+            if i != c and i not in closed:
+                w.write(b"PING\r\n")
+        for i in range(len(conns)):
+            if i not in closed:
+                await read_to_pong(i)
     for op in script:
         kind, c = op[0], op[1]
         if c in closed:
             continue
-        w = conns[c][1]
         if kind == "sub":
-            w.write(f"SUB {op[2]} {op[3]}\r\n".encode())
+            data = f"SUB {op[2]} {op[3]}\r\n".encode()
         elif kind == "pub":
-            w.write(f"PUB {op[2]} _INBOX.r {len(op[3])}\r\n".encode() + op[3] + b"\r\n")
+            data = f"PUB {op[2]} _INBOX.r {len(op[3])}\r\n".encode() + op[3] + b"\r\n"
         elif kind == "hpub":
             h = b"NATS/1.0\r\nk: v\r\n\r\n"
-            w.write(f"HPUB {op[2]} {len(h)} {len(h) + len(op[3])}\r\n".encode() + h + op[3] + b"\r\n")
+            data = f"HPUB {op[2]} {len(h)} {len(h) + len(op[3])}\r\n".encode() + h + op[3] + b"\r\n"
         elif kind == "unsub":
-            w.write(f"UNSUB {op[2]} {op[3]}\r\n".encode() if op[3] else f"UNSUB {op[2]}\r\n".encode())
+            data = f"UNSUB {op[2]} {op[3]}\r\n".encode() if op[3] else f"UNSUB {op[2]}\r\n".encode()
         else:
-            w.write(f"PUB {op[2]} 0\r\n\r\n".encode())
-        await sync()
+            data = f"PUB {op[2]} 0\r\n\r\n".encode()
+        await sync(c, data)
     for _, w in conns:
         w.close()
     await b.stop()
@@ -271,6 +283,10 @@ async def _script_output(Broker, script):
 # a reused sid re-subscribed after a wildcard sub: delivery follows creation order, not sid order
 @example([("sub", 0, "a", 1), ("unsub", 0, 1, 0), ("sub", 0, "*.*.*", 2), ("sub", 1, "*", 1),
           ("sub", 0, "a.b.b", 1), ("pub", 0, "a.b.b", b"")])
+# a delivered payload that reads like the sync marker, then a protocol error that closes a connection
+@example([("sub", 0, "a", 1), ("pub", 0, "a", b"PONG\r\n"), ("sub", 0, "*", 1), ("bad", 0, " ", b""),
+          ("unsub", 0, 1, 0), ("pub", 1, "a", b"PONG\r\n")])
+@example([("sub", 0, "a", 1), ("pub", 0, "a", b"PONG\r\n"), ("bad", 1, " ", b"")])
 def test_native_broker_matches_reference_on_random_scripts(script):
     py = run(_script_output(BROKERS["py"], script))
     nat = run(_script_output(BROKERS["native"], script))

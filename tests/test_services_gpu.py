@@ -76,18 +76,23 @@ def test_ingest_and_search_on_gpu():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("extra,debug", [([], False), (["--opt", "overlap=0"], False), ([], True),
+@pytest.mark.parametrize("extra,debug", [(["--full"], False),
+                                         (["--full", "--opt", "overlap=0"], False),
+                                         (["--full"], True),
                                          (["--mode", "embed"], False),
-                                         (["--mode", "embed", "--opt", "graph=0"], False)])
-def test_bench_contract_small_index(extra, debug):
+                                         (["--mode", "embed", "--opt", "graph=0"], False),
+                                         (["--dump-outputs", "DIR"], False)])
+def test_bench_contract_small_index(extra, debug, tmp_path):
     """bench.py's driver contract (one JSON line, whole-job value, step timing) on a small index,
-    with and without the encode/search stream overlap."""
+    with and without the encode/search stream overlap; the held-out search rate with --full only;
+    --dump-outputs writes the last timed step's arrays."""
     import json
     import os
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    extra = [str(tmp_path) if a == "DIR" else a for a in extra]
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3",
                           "--warmup", "2", "--index-rows", "2000000"] + extra,
                          capture_output=True, text=True, timeout=300, cwd=root,
@@ -103,9 +108,33 @@ def test_bench_contract_small_index(extra, debug):
     assert ("overlap" in r["config"]) is ("overlap=0" in extra)
     assert r["config"].get("encoder_hipgraph", False) is ("--mode" in extra
                                                           and "graph=0" not in extra and not debug)
-    if "--mode" not in extra:   # the held-out search rate rides in the headline's line
-        assert r["heldout_searches"] == 20 and r["heldout_topk_qps"] > 0
+    if "--mode" not in extra:
         assert "stream scan" in r["config"]["index_scan"]
+    if "--full" in extra:       # the held-out search rate rides in the headline's line
+        assert r["heldout_searches"] == 20 and r["heldout_topk_qps"] > 0
+    else:                       # a plain run times its steps and nothing more
+        assert not [k for k in r if k.startswith("heldout_")]
+    if "--dump-outputs" in extra:
+        import numpy as np
+
+        got = {f.name: np.load(f) for f in tmp_path.iterdir()}
+        assert {n: (a.shape, a.dtype) for n, a in got.items()} == {
+            "embeddings.npy": ((256, 384), np.float32),
+            "unit_embeddings.npy": ((256, 384), np.float32),
+            "topk_scores.npy": ((256, 10), np.float32),
+            "topk_ids.npy": ((256, 10), np.float64)}
+        assert all(np.isfinite(a).all() for a in got.values())
+        # the unit embeddings are the pooled ones normalised (bf16: 2^-8 relative steps)
+        e = got["embeddings.npy"]
+        assert np.abs(e / np.linalg.norm(e, axis=1, keepdims=True)
+                      - got["unit_embeddings.npy"]).max() < 2.0 ** -7
+        # the batch was upserted before it was searched, so every query's best score is its own
+        # row's (or a near-duplicate's): 1 up to the bf16 rounding of the unit rows; the lists
+        # are sorted and name rows of the shard (2M corpus rows + at most 7 batches in flight)
+        s, ids = got["topk_scores.npy"], got["topk_ids.npy"]
+        assert np.abs(s[:, 0] - 1.0).max() < 2.0 ** -6
+        assert (np.diff(s, axis=1) <= 0).all()
+        assert (ids == np.floor(ids)).all() and ids.min() >= 0 and ids.max() < 2_000_000 + 7 * 256
 
 
 @pytest.mark.gpu
