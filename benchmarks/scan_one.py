@@ -3,13 +3,12 @@
 the target of timing A/Bs and rocprofv3 --pmc passes (benchmarks/pmc_kernel.py --match scan).
 
     python benchmarks/scan_one.py [--rows 25000000] [--nq 256] [--corpus random] [--iters 10]
-                                  [--tier i8|mx4|mx6] [--queries heldout|self]
+                                  [--tier i8|mx4] [--queries heldout|self]
 
 The shard's scan is the stream scan (index_stream.hip) unless SYMB_PRUNE_STREAM=0 (the round-4
 LDS-ring scan, index_i8.hip).  --tier mx4 times the MX-fp4 first tier on the same block grid with
 the thresholds the tier choice computed (--queries self: stored rows as queries; near: near-duplicate queries, whose sets the centroid
-test skips; both at the headline's fp4 threshold 0.74).  --tier mx6 times the MX-fp6 middle tier
-(SYMB_PRUNE_MX6) at the thresholds its tier choice computed.
+test skips; both at the headline's fp4 threshold 0.74).
 """
 from __future__ import annotations
 
@@ -31,7 +30,7 @@ def main() -> None:
     ap.add_argument("--dim", type=int, default=384)
     ap.add_argument("--corpus", default="random")
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--tier", choices=["i8", "mx4", "mx6"], default="i8")
+    ap.add_argument("--tier", choices=["i8", "mx4"], default="i8")
     ap.add_argument("--queries", choices=["heldout", "self", "near"], default="heldout")
     ap.add_argument("--ab", default="",
                     help="stream forms timed in one process, interleaved: comma list of "
@@ -68,34 +67,23 @@ def main() -> None:
     P, n = shard._pruned_last, shard.visible
     rsplit = 2 if a.nq < 512 else 1
     heavy = P["heavy"]
-    m4, m6 = P["m4"], P.get("m6")
+    m4 = P["m4"]
     if a.tier == "mx4" and m4 is None:
         raise SystemExit("no MX-fp4 tier on this shard")
-    if a.tier == "mx6" and m6 is None:
-        raise SystemExit("no MX-fp6 tier on this shard")
     if a.tier == "mx4" and a.queries in ("self", "near"):
         # the headline's batches take the fp4 tier because their k-th scores sit near 0.99 (fresh
         # near-duplicate embeddings): T - margin4 ~ 0.74.  Stored random rows as queries have
         # k-th scores ~0.2 (only the row itself scores high), for which the tier is never chosen;
         # time the kernel at the headline's threshold instead
         m4["thr4"].fill_(0.74)
-    if a.tier == "mx6" and a.queries in ("self", "near"):
-        m6["thr6"].fill_(0.74)   # (kernel timing at the headline's threshold, as for mx4)
     if a.thr_add:
-        for t in (P["thr"], m4 and m4.get("thr4"), m6 and m6.get("thr6")):
+        for t in (P["thr"], m4 and m4.get("thr4")):
             if t is not None:
                 t.add_(a.thr_add)
     nbytes = 0
 
     def scan():
-        if a.tier == "mx6":
-            P["cnt"].zero_()
-            h.index_scan_stream(shard.img_mx6.data_ptr(), n, shard.img_mx6.shape[0] * STREAM_SUB,
-                                P["rows_per_blk"], P["n_rblk"], m6["q6"].data_ptr(),
-                                m6["qs6"].data_ptr(), a.nq, m6["thr6"].data_ptr(),
-                                P["cs"].data_ptr(), P["ci"].data_ptr(), P["cnt"].data_ptr(),
-                                P["cap"], 1, st, dim=a.dim, form=2)
-        elif a.tier == "mx4":
+        if a.tier == "mx4":
             P["cnt"].zero_()
             if shard.img_mx4 is not None:
                 h.index_scan_stream(shard.img_mx4.data_ptr(), n, shard.img_mx4.shape[0] * STREAM_SUB,
@@ -122,9 +110,7 @@ def main() -> None:
                             P["ci"].data_ptr(), P["cnt"].data_ptr(), P["cap"], 1, st, rsplit,
                             dim=a.dim, heavy=heavy, sq=P["sq"].data_ptr() if heavy else 0)
 
-    if a.tier == "mx6":
-        nbytes, kernel = shard.img_mx6.shape[1] / STREAM_SUB, "stream-mx6"
-    elif a.tier == "mx4":
+    if a.tier == "mx4":
         nbytes = (shard.img_mx4.shape[1] / STREAM_SUB if shard.img_mx4 is not None
                   else a.dim // 2 + 16)
         kernel = "stream-mx4" if shard.img_mx4 is not None else "ldsring-mx4"

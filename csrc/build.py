@@ -69,8 +69,8 @@ def _compile_all(jobs: list[tuple[list[str], Path, Path, float]], nproc: int, fo
 
 # per-file code-generation flags.  The stream scans keep their MFMA accumulators in VGPRs
 # (`-amdgpu-mfma-vgpr-form`): the default AGPR form copied operands and results through
-# v_accvgpr moves in the hot loop -- 100M x 384 int8 scan 11.36 -> 10.94 ms, MX-fp4 5.59 -> 5.05,
-# MX-fp6 7.26 -> 6.67 (profiles/r5_scan/ab_vgpr_form.jsonl)
+# v_accvgpr moves in the hot loop -- 100M x 384 int8 scan 11.36 -> 10.94 ms, MX-fp4 5.59 -> 5.05
+# (profiles/r5_scan/ab_vgpr_form.jsonl)
 FILE_FLAGS = {"index_stream.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 

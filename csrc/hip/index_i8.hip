@@ -36,16 +36,13 @@ constexpr int WAVES = 8;
 constexpr int SETS = 4;                     // 16-query sets per wave
 constexpr int SUB = 16;
 constexpr int PIECE = 1024;
-#ifndef SYMB_I8_PF
-#define SYMB_I8_PF 5
-#endif
 }  // namespace i8s
 
 // Row width: D = 384 (the headline shard) or 768 (the reference's collection,
 // vector_memory_service/src/main.rs:22).  v_mfma_i32_16x16x64_i8 k-steps: 6 / 12; the queries'
 // B fragments take SETS x NKS x 4 = 96 / 192 VGPRs.
-// Fragment reads in flight: PF (NKS % (PF + 1) == 0); 3 at D = 768, whose 192 query registers
-// leave no room for a 6-slot fragment ring.
+// Fragment reads in flight: PF (NKS % (PF + 1) == 0); 5 at D = 384, 3 at D = 768, whose 192 query
+// registers leave no room for a 6-slot fragment ring.
 // HK > 0: the SPLIT image (see "split image" below): the first 32 * HK dims of each (rotated) row
 // as fp16, HK v_mfma_f32_16x16x32_f16 k-steps of 64 bytes, then the other D - 32 * HK dims as
 // int8 -- RB = 448 bytes per 384-wide row.  Only the fused two-sub-tile chains run it.
@@ -56,7 +53,7 @@ constexpr int MX4 = 4;
 template <int D, int HK = 0> struct I8Dim {
   static constexpr int NKS = HK == MX4 ? D / 128 : (D + 32 * HK) / 64;
   static constexpr int RB = NKS * 64;            // image bytes per row
-  static constexpr int PF = HK ? NKS - 1 : (D == 384 ? SYMB_I8_PF : 3);
+  static constexpr int PF = HK ? NKS - 1 : (D == 384 ? 5 : 3);
   static constexpr int R = PF + 1;
   static_assert(D == 384 || D == 768, "int8 scan row width");
   static_assert(HK == 0 || (D == 384 && (HK == 2 || HK == MX4)),
@@ -263,9 +260,6 @@ __device__ __forceinline__ const char* i8_uniform(const char* p) {
 // X8: [>= round_up(n_valid, 64), 384] int8 rows; sx: their scales (f32, same padding);
 // Q8: [NQ, 384] int8 queries; thr[NQ]: emit a row iff (q8 . x8) * sx >= thr (already divided by
 // the query's scale).  cand_s/cand_i: [NQ][cap]; cand_n[NQ] zeroed by the host entry.
-// ABL (profiling entry symb_index_scan_i8_ablate only): 1 = no LDS-DMA, 2 = no emission test,
-// 3 = full + s_memtime / s_memrealtime around the tile loop into cand_s[2 * blockIdx.x + {0, 1}],
-// 4 = LDS-DMA ring only.
 //
 // HK = 2 (the split image, index/shard.py calibrate_prune): rows and queries are rotated by the
 // shard's orthogonal PCA basis, the 64 leading components are kept as fp16 (an fp32 MFMA dot, ~11
@@ -281,7 +275,7 @@ __device__ __forceinline__ const char* i8_uniform(const char* p) {
 // The MFMA applies the scales, so acc_f is the approximate score itself: emit iff acc_f >= thr
 // (thr = T - margin in score units, the bound of quant_rows_mx4).
 // gate (optional): the kernel runs only if *gate == gate_want (the device-side tier choice).
-template <int D, int RSPLIT, int ABL = 0, int TRK = 64, int WV = 8, int HK = 0>
+template <int D, int RSPLIT, int TRK = 64, int WV = 8, int HK = 0>
 __global__ __launch_bounds__(64 * WV, 8 / WV) void index_scan_i8_kernel(
     const int8_t* __restrict__ X8, const float* __restrict__ sx, int n_valid, int rows_per_blk,
     const int8_t* __restrict__ Q8, int NQ, int n_qblk, int xcd, const float* __restrict__ thr_in,
@@ -451,11 +445,6 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void index_scan_i8_kernel(
   // compare; a set with thr <= 0 always takes the exact test
   auto emit = [&](i32x4 (&acc)[SETS], int row0, const f32x4 s4) {
     fence_acc(acc, acc);
-    if constexpr (ABL == 2 || ABL == 4) {
-#pragma unroll
-      for (int s = 0; s < SETS; ++s) asm volatile("" ::"v"(acc[s]), "v"(s4));
-      return;
-    }
     const float rs = __builtin_amdgcn_rcpf(fmaxf(fmaxf(s4[0], s4[1]), fmaxf(s4[2], s4[3])));
     bool hs[SETS];
     bool hit = false;
@@ -482,11 +471,6 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void index_scan_i8_kernel(
   auto emit2 = [&](i32x4 (&acc)[2][SETS], auto& af, int row0, const f32x4 sa, const f32x4 sb) {
     fence_acc(acc[0], af[0]);
     fence_acc(acc[1], af[HK ? 1 : 0]);
-    if constexpr (ABL == 2 || ABL == 4) {
-#pragma unroll
-      for (int s = 0; s < SETS; ++s) asm volatile("" ::"v"(acc[0][s]), "v"(acc[1][s]), "v"(sa), "v"(sb));
-      return;
-    }
     bool hs[SETS];
 #pragma unroll
     for (int s = 0; s < SETS; ++s) hs[s] = true;
@@ -531,16 +515,11 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void index_scan_i8_kernel(
 
   // the scale waves carry one extra vector-memory op per tile
   constexpr int W0X = 1;
-  if (n_tiles > 0 && ABL != 1) {
+  if (n_tiles > 0) {
 #pragma unroll
     for (int p = 0; p < NS - 1; ++p)
 #pragma unroll
       for (int i = 0; i < LOADS; ++i) issue_tile(p, i);
-  }
-  uint64_t c0 = 0, r0t = 0;
-  if constexpr (ABL == 3) {
-    c0 = __builtin_amdgcn_s_memtime();
-    r0t = __builtin_amdgcn_s_memrealtime();
   }
   i32x4 a[I8Dim<D>::R];
   i32x4 acc[SETS];
@@ -563,30 +542,21 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void index_scan_i8_kernel(
   // refilling that tile's scale slot: its scales are read into registers before the barrier
   f32x4 s4_last = {0.f, 0.f, 0.f, 0.f};
   for (int t = 0; t < n_tiles; ++t) {
-    if constexpr (ABL != 1) {
-      if (wave_u < G::SCW)
-        wait_vmcnt<(LOADS + W0X) * (NS - 2)>();
-      else if (G::FULLW == WV || wave_u < G::FULLW)
-        wait_vmcnt<LOADS * (NS - 2)>();
-      else   // (split image: the waves carrying one piece fewer per tile)
-        wait_vmcnt<(LOADS - 1) * (NS - 2)>();
-    }
+    if (wave_u < G::SCW)
+      wait_vmcnt<(LOADS + W0X) * (NS - 2)>();
+    else if (G::FULLW == WV || wave_u < G::FULLW)
+      wait_vmcnt<LOADS * (NS - 2)>();
+    else   // (split image: the waves carrying one piece fewer per tile)
+      wait_vmcnt<(LOADS - 1) * (NS - 2)>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     const int slot = t % NS;
     const uint32_t tbase = lds_smem + (uint32_t)(slot * TILE_BYTES);
     const int row0 = row_begin + t * TR;
     const int tnext = t + NS - 1;
-    auto dma = [&](int i) {
-      if constexpr (ABL != 1) issue_tile(tnext, i);
-    };
+    auto dma = [&](int i) { issue_tile(tnext, i); };
     const uint32_t fw = tbase + foff + j0 * NKS * PIECE;
     const int last = (j0 + NSW - 1) * SUB;
-    if constexpr (ABL == 4) {
-#pragma unroll
-      for (int i = 0; i < LOADS; ++i) dma(i);
-      continue;
-    }
     if constexpr (FUSE) {
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
@@ -657,14 +627,6 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void index_scan_i8_kernel(
   }
   if (nst) flush();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if constexpr (ABL == 3) {
-    const uint64_t cyc = __builtin_amdgcn_s_memtime() - c0;
-    const uint64_t rt = __builtin_amdgcn_s_memrealtime() - r0t;
-    if (tid == 0) {
-      cand_s[2 * blockIdx.x] = (float)cyc;
-      cand_s[2 * blockIdx.x + 1] = (float)rt;
-    }
-  }
 }
 
 // Exact re-score of every candidate: cand_s[q][c] = <Q[q], X[cand_i[q][c]]> over the bf16 rows
@@ -1113,27 +1075,20 @@ __global__ __launch_bounds__(256) void quant_rows_mx4_kernel(const __bf16* __res
 // runs at thr4 = T - margin4).  Exactness never depends on the choice.
 // probe_s: [NQ][ld] exact scores; the probe is columns c < n_cols whose 64-row tile c / 64 is a
 // multiple of tile_stride (1: every column), scaled by `rate`; tail_cs: [NQ][tail_ld].
-// stage (the MX-fp6 tier between the two, margin4 then being the fp6 margin): 0 = the fp4 choice
-// (bit 0 of *nv: fp4 not viable); 1 = the fp6 choice after the fp4 one (nothing when fp4 runs,
-// else bit 1: fp6 not viable); 2 = the fp6 choice alone (bit 0 always, bit 1 as in 1).  The
-// gated scans then want *nv == 0 (fp4), 1 (fp6), 3 (int8).
-// The band counted is [T - wa margin4 - wb margin8, T - margin8): (2, 0) -- the fp4 tier's
-// worst case -- or (1, 0) for the fp6 tier, whose rounding error on a pair is typically ~1/30 of
-// its Cauchy-Schwarz bound, so its emissions are ~ the rows above T - margin6 (an underestimate
-// only costs the overflow fallback, never exactness; the limit leaves 4x headroom to the cap).
+// The band counted is [T - 2 margin4, T - margin8), the fp4 tier's worst case.  (The kernel once
+// took band weights, lo = T - wa margin4 - wb margin8 with (wa, wb) = (2, 0); the wb = 0 term
+// vanished exactly because margins are finite, so lo is the same float.)
 __global__ __launch_bounds__(256) void mx4_select_kernel(
     int NQ, const float* __restrict__ T, const float* __restrict__ margin4,
     const float* __restrict__ margin8, const float* __restrict__ probe_s, int n_cols, int ld,
     int tile_stride, float rate, const float* __restrict__ tail_cs, int tail_cap, int tail_ld,
-    float limit, float* __restrict__ thr4, int* __restrict__ nv, int stage, float wa, float wb) {
+    float limit, float* __restrict__ thr4, int* __restrict__ nv) {
   // one 256-thread workgroup per query (a wave per query took 146 us for 256 queries)
   __shared__ float red[2][4];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int q = blockIdx.x;
-  if (stage == 1 && (*nv & 1) == 0) return;   // (bit 0 is final: the fp4 choice ran before)
-  if (stage == 2 && q == 0 && threadIdx.x == 0) atomicOr(nv, 1);
   const float t = T[q];
-  const float lo = t - wa * margin4[q] - wb * margin8[q], hi = t - margin8[q];
+  const float lo = t - 2.f * margin4[q], hi = t - margin8[q];
   // the probe's columns enumerated directly (probe tile j = tile j * tile_stride), four
   // independent loads in flight per thread: the walk over every column with a per-element tile
   // test waited out one load round trip per probe column (97 us per held-out search)
@@ -1179,7 +1134,7 @@ __global__ __launch_bounds__(256) void mx4_select_kernel(
     c = red[0][0] + red[0][1] + red[0][2] + red[0][3];
     tc = red[1][0] + red[1][1] + red[1][2] + red[1][3];
     thr4[q] = t - margin4[q];
-    if (!(c * rate + tc <= limit)) atomicOr(nv, stage ? 2 : 1);
+    if (!(c * rate + tc <= limit)) atomicOr(nv, 1);
   }
 }
 
@@ -1424,8 +1379,8 @@ static int launch_i8(const void* X8, const float* sx, int n_valid, int rows_per_
                        xcd, thr, cand_s, cand_i, cand_n, cap, skip, sq, gate, gate_want);
     return (int)hipGetLastError();
   };
-  return go(std::integral_constant<decltype(&index_scan_i8_kernel<D, RSPLIT, 0, TRK, WV, HK>),
-                                   &index_scan_i8_kernel<D, RSPLIT, 0, TRK, WV, HK>>());
+  return go(std::integral_constant<decltype(&index_scan_i8_kernel<D, RSPLIT, TRK, WV, HK>),
+                                   &index_scan_i8_kernel<D, RSPLIT, TRK, WV, HK>>());
 }
 
 // Tile rows the D-wide scan runs with (the 128-row and 4-wave forms are D = 384 knobs; the split
@@ -1491,54 +1446,6 @@ int symb_index_scan_i8(const void* X8, const float* sx, int n_valid, int alloc_r
   if (rsplit == 1) return SYMB_I8(384, 1, 64);
 #undef SYMB_I8
   return -1;
-}
-
-// Profiling-only entry: the ablations of index_scan_i8_kernel<384, 2> (ABL above), same arguments.
-int symb_index_scan_i8_ablate(const void* X8, const float* sx, int n_valid, int alloc_rows,
-                              int rows_per_blk, int n_rblk, const void* Q8, int NQ,
-                              const float* thr, float* cand_s, int* cand_i, int* cand_n, int cap,
-                              int xcd, hipStream_t st, int abl) {
-  if (NQ <= 0) return 0;
-  const int tr = g_i8_tr;
-  if (rows_per_blk % tr || n_rblk <= 0 || thr == nullptr || cap <= 0 || n_valid <= 0) return -1;
-  if ((long long)n_rblk * rows_per_blk < n_valid) return -1;
-  if ((long long)(n_valid + tr - 1) / tr * tr > alloc_rows) return -1;
-  hipError_t e = hipMemsetAsync(cand_n, 0, sizeof(int) * (size_t)NQ, st);
-  if (e != hipSuccess) return (int)e;
-  const int n_qblk = (NQ + 255) / 256;
-  const int w4 = g_i8_waves == 4;
-  const int lds = w4 ? Geo<384, 64, 4>::LDS_BYTES
-                     : (tr == 128 ? Geo<384, 128>::LDS_BYTES : Geo<384, 64>::LDS_BYTES);
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL(kern, dim3(n_rblk * n_qblk), dim3(w4 ? 256 : 512), lds, st, (const int8_t*)X8, sx,
-                       n_valid, rows_per_blk, (const int8_t*)Q8, NQ, n_qblk, xcd, thr, cand_s,
-                       cand_i, cand_n, cap, (const int*)nullptr, (const float*)nullptr,
-                       (const int*)nullptr, 0);
-    return (int)hipGetLastError();
-  };
-  if (w4) {
-    switch (abl) {
-      case 0: return go(index_scan_i8_kernel<384, 1, 0, 64, 4>);
-      case 2: return go(index_scan_i8_kernel<384, 1, 2, 64, 4>);
-      case 3: return go(index_scan_i8_kernel<384, 1, 3, 64, 4>);
-      case 4: return go(index_scan_i8_kernel<384, 1, 4, 64, 4>);
-      default: return -1;
-    }
-  }
-  switch (abl + (tr == 128 ? 8 : 0)) {
-    case 0: return go(index_scan_i8_kernel<384, 2, 0, 64>);
-    case 1: return go(index_scan_i8_kernel<384, 2, 1, 64>);
-    case 2: return go(index_scan_i8_kernel<384, 2, 2, 64>);
-    case 3: return go(index_scan_i8_kernel<384, 2, 3, 64>);
-    case 4: return go(index_scan_i8_kernel<384, 2, 4, 64>);
-    case 8: return go(index_scan_i8_kernel<384, 2, 0, 128>);
-    case 9: return go(index_scan_i8_kernel<384, 2, 1, 128>);
-    case 10: return go(index_scan_i8_kernel<384, 2, 2, 128>);
-    case 11: return go(index_scan_i8_kernel<384, 2, 3, 128>);
-    case 12: return go(index_scan_i8_kernel<384, 2, 4, 128>);
-    default: return -1;
-  }
 }
 
 // launch F(D) for the shard's row width (D = 384 / 768 / 1024); -1 for any other
@@ -1610,9 +1517,8 @@ int symb_prune_stats(const int* ovf, const int* cnt, int NQ, const int* dense, c
 int symb_mx4_select(int NQ, const float* T, const float* margin4, const float* margin8,
                     const float* probe_s, int n_cols, int ld, int tile_stride, float rate,
                     const float* tail_cs, int tail_cap, int tail_ld, float limit, float* thr4,
-                    int* nv, hipStream_t st, int nv_zeroed, int stage, float wa, float wb) {
+                    int* nv, hipStream_t st, int nv_zeroed) {
   if (NQ <= 0) return 0;
-  if (stage < 0 || stage > 2 || (stage == 1 && !nv_zeroed)) return -1;
   if (ld <= 0) ld = n_cols;
   if (tail_ld <= 0) tail_ld = tail_cap;
   if (n_cols <= 0 || ld < n_cols || tile_stride < 1 || tail_cap < 0 || tail_ld < tail_cap ||
@@ -1624,7 +1530,7 @@ int symb_mx4_select(int NQ, const float* T, const float* margin4, const float* m
   }
   hipLaunchKernelGGL(mx4_select_kernel, dim3(NQ), dim3(256), 0, st, NQ, T, margin4, margin8,
                      probe_s, n_cols, ld, tile_stride, rate, tail_cs, tail_cap, tail_ld, limit,
-                     thr4, nv, stage, wa, wb);
+                     thr4, nv);
   return (int)hipGetLastError();
 }
 
