@@ -136,8 +136,13 @@ FP8_DIMS = (256, 384, 512, 768, 1024)   # row widths the fp8 scan kernel takes
 MQ_DIMS = (384, 768, 1024)              # ... the emitting bf16 scan (index_mq.hip)
 PRUNE_DIMS = (384, 768, 1024)           # ... the int8-pruned scan (1024: stream scan only)
 AUTO_PRUNE_DIMS = (384, 768)            # ... where SYMB_INDEX_PRUNE=auto takes it
-SPLIT_DIMS = (384,)                     # ... its split image (calibrate_prune)
-SPLIT_HEAVY = 64                        # leading components the split image keeps as fp16
+SPLIT_DIMS = (384, 768)                 # ... its split image (calibrate_prune)
+# ... where a shard takes the split image by itself (SYMB_I8_SPLIT=auto, the write-time triggers);
+# at 768 only an explicit calibrate_prune() or SYMB_I8_SPLIT=on does (profiles/r7_split768/)
+AUTO_SPLIT_DIMS = (384,)
+# leading components the split image keeps as fp16, per row width (768: 13 k-steps of 64 bytes;
+# 128 would bound slightly tighter for 8 % more image bytes, profiles/r7_split768/)
+SPLIT_HEAVY = {384: 64, 768: 64}
 MX4_DIMS = (384, 768, 1024)             # ... the MX-fp4 first tier (384-only on the LDS-ring scan)
 # widths of the streaming pruning scan (index_stream.hip): fragment-major int8 / MX-fp4 images,
 # one wave per SIMD, no LDS ring (SYMB_PRUNE_STREAM=0: the round-4 LDS-ring scan, index_i8.hip,
@@ -200,8 +205,11 @@ class HbmIndexShard:
         # search (csrc/hip/index_i8.hip), plus the two global maxima its error bound needs:
         # E = max |x - x~| and X = max |x~| over every row ever written (monotone, so conservative)
         self.rows_i8 = self.sx_i8 = self.i8_bounds = None
-        # the image's form (calibrate_prune): 0 = plain int8 rows; SPLIT_HEAVY = the split image
-        # of PCA-rotated rows (leading components fp16, the rest int8) for anisotropic corpora
+        # the image's form (calibrate_prune): 0 = plain int8 rows; SPLIT_HEAVY[dim] = the split
+        # image of PCA-rotated rows (leading components fp16, the rest int8) for anisotropic
+        # corpora.  SYMB_I8_SPLIT: "auto" (default) = chosen by the rows' spectrum, at write time
+        # for the widths in AUTO_SPLIT_DIMS and by an explicit calibrate_prune() for every width
+        # in SPLIT_DIMS; "on" = forced at every width in SPLIT_DIMS; "off" = always plain
         self.i8_split = os.environ.get("SYMB_I8_SPLIT", "auto").strip().lower()
         self._i8_heavy = 0
         self._i8_rot = None          # fp64 [D, D] orthogonal basis (rows: components) or None
@@ -223,14 +231,12 @@ class HbmIndexShard:
         self.img_i8 = self.img_mx4 = None
         if prune:
             # padded to whole 128-row tiles: the int8 scan's DMA reads whole tiles; one flat byte
-            # store sized for the widest form that applies (viewed per form)
+            # store (viewed per form), at 384 sized for the widest form that applies, at 768 for
+            # the form in use (_i8_store_bytes)
             n_alloc = _round_up(self.rows.shape[0], 128)
-            rb = dim + SPLIT_HEAVY if dim in SPLIT_DIMS else dim
-            nbytes = n_alloc * rb
-            if self.stream and not self.i8_ring:
-                nbytes = max(nbytes, n_alloc // STREAM_SUB * self._stream_rec(0))
-            self._i8_store = torch.zeros(nbytes, dtype=torch.int8, device=self.device)
             self.sx_i8 = torch.ones(n_alloc, dtype=torch.float32, device=self.device)
+            self._i8_store = torch.zeros(self._i8_store_bytes(0), dtype=torch.int8,
+                                         device=self.device)
             self._set_i8_view(0)
             # (E, X) of the plain form; (E_l, X_l, E_h, X_h) of the split form
             self.i8_bounds = torch.zeros(4, dtype=torch.float32, device=self.device)
@@ -306,10 +312,28 @@ class HbmIndexShard:
         nks = self.dim // (64 if form else 32)
         return nks * 1024 + ((nks + 3) // 4 * 256 if form else 16)
 
+    def _i8_store_bytes(self, heavy: int) -> int:
+        """Bytes of the flat int8 store for the form.  A 384-wide shard keeps one store sized for
+        its widest form; wider shards (100M x 768 fills most of a card) hold only the form in
+        use, so one that stays plain pays nothing for the split image."""
+        n_alloc = self.sx_i8.shape[0]
+        if self.dim == 384:
+            heavy = SPLIT_HEAVY[384]
+        nbytes = n_alloc * (self.dim + heavy)
+        if self.stream and not self.i8_ring and (self.dim == 384 or not heavy):
+            nbytes = max(nbytes, n_alloc // STREAM_SUB * self._stream_rec(0))
+        return nbytes
+
     def _set_i8_view(self, heavy: int) -> None:
         """Views of the flat int8 store for the form: the stream image (plain form on a stream
-        shard) or the row-major image [n_alloc, D + heavy] (split form, or stream off)."""
+        shard) or the row-major image [n_alloc, D + heavy] (split form, or stream off).  A store
+        of another form's size is released first, then allocated anew (the caller re-images
+        every row)."""
         n_alloc = self.sx_i8.shape[0]
+        nbytes = self._i8_store_bytes(heavy)
+        if self._i8_store.numel() != nbytes:
+            self._i8_store = self.rows_i8 = self.img_i8 = None
+            self._i8_store = torch.zeros(nbytes, dtype=torch.int8, device=self.device)
         if self.stream and not heavy and not self.i8_ring:
             rec = self._stream_rec(0)
             self.img_i8 = self._i8_store[:n_alloc // STREAM_SUB * rec].view(torch.uint8).view(
@@ -483,7 +507,7 @@ class HbmIndexShard:
                 or self.dim not in STREAM_DIMS or self.mx4_on != (self.img_mx4 is not None)):
             return False
         due = r0 + n >= self._calib_next or (self.i8_split == "on" and not self._i8_heavy)
-        if due and self.i8_split != "off" and self.dim in SPLIT_DIMS:
+        if due and self._split_at_write():
             return False
         if (src.device != self.device or src.dtype != torch.bfloat16 or not src.is_contiguous()
                 or src.shape[-1] != self.dim):
@@ -497,13 +521,20 @@ class HbmIndexShard:
                           self.mx4_bounds.data_ptr() if m4 else 0, stream_handle(self.device))
         return True
 
+    def _split_at_write(self) -> bool:
+        """The write-time triggers may (re-)calibrate this shard's image: SYMB_I8_SPLIT=on at every
+        width the split image exists for, auto only where a shard changes form by itself."""
+        if self.i8_split == "off":
+            return False
+        return self.dim in (SPLIT_DIMS if self.i8_split == "on" else AUTO_SPLIT_DIMS)
+
     def rows_written(self, r0: int, n: int) -> None:
         """bf16 rows [r0, r0+n) changed: refresh their e4m3 prefilter image and their int8
         pruning image (no-ops without them).  Callers that write ``rows`` directly (snapshot loads)
         must call this too."""
         if self.prune_on and n > 0:
             due = r0 + n >= self._calib_next or (self.i8_split == "on" and not self._i8_heavy)
-            if due and self.i8_split != "off" and self.dim in SPLIT_DIMS:
+            if due and self._split_at_write():
                 # (re-images every row below r0 + n when the image's form changes; the new
                 # rows' MX-fp4 image below)
                 self.calibrate_prune(r0 + n, lo=r0)
@@ -567,9 +598,9 @@ class HbmIndexShard:
             m2 = smp.t() @ smp / smp.shape[0]
             ev, vec = torch.linalg.eigh(m2)                 # ascending
             ev, vec = ev.flip(0), vec.flip(1)
-            share = float(ev[:SPLIT_HEAVY].sum() / ev.sum().clamp_min(1e-30))
+            share = float(ev[:SPLIT_HEAVY[self.dim]].sum() / ev.sum().clamp_min(1e-30))
             if self.i8_split == "on" or share >= self.SPLIT_MIN_SHARE:
-                heavy, rot = SPLIT_HEAVY, vec.t().contiguous()
+                heavy, rot = SPLIT_HEAVY[self.dim], vec.t().contiguous()
         # (the int8 / split image only)
         mx4_saved, self.mx4_bounds = self.mx4_bounds, None
         try:
@@ -684,7 +715,8 @@ class HbmIndexShard:
         if not self._i8_heavy:
             self._quant_i8(src, dst8, scale, bounds)
             return
-        chunk = 1 << 18      # bounds the fp64 / fp32 rotation temporaries (~1.2 GB at 384)
+        # bounds the fp64 / fp32 rotation temporaries (~1.2 GB at every width)
+        chunk = max(1, (1 << 18) * 384 // self.dim)
         for s in range(0, n, chunk):
             e = min(n, s + chunk)
             xr = self._rotate(src[s:e])
@@ -1316,13 +1348,17 @@ class HbmIndexShard:
         h = hip()
         heavy = self._i8_heavy
         rsplit = 2 if (NQ < 512 or self.i8_rsplit2) else 1
+        if heavy and self.dim == 768:
+            # (2 query sets per wave: the row-split form holds 128 queries per workgroup, the
+            # other 256 -- a larger batch streams each row tile once per 256 queries)
+            rsplit = 2 if (NQ <= h.i8_split_queries_per_blk(2, self.dim) or self.i8_rsplit2) else 1
         if self.stream:
             # the stream scans (one wave per SIMD): one block grid for both tiers, sized for the
             # tier with more workgroups per CU; rows_per_blk a multiple of 128 (the bf16 list
             # scan of routed blocks reads 64-row tiles).  A split-form shard runs its int8 tier
             # on the LDS-ring kernel: 64-row tiles there too.
             if heavy:
-                n_qblk, wpc = math.ceil(NQ / h.i8_split_queries_per_blk(rsplit)), 1
+                n_qblk, wpc = math.ceil(NQ / h.i8_split_queries_per_blk(rsplit, self.dim)), 1
             elif self.i8_ring:   # (the LDS-ring int8 scan beside the stream fp4 tier)
                 n_qblk, wpc = math.ceil(NQ / h.i8_queries_per_blk(rsplit)), h.i8_wgs_per_cu()
             else:
@@ -1342,7 +1378,7 @@ class HbmIndexShard:
         if self.mx4_on and rsplit == 2:   # (one block grid for both tiers)
             tr = max(tr, h.mx4_tile_rows())
         if heavy:   # (the split image always runs 8-wave workgroups, one per CU)
-            n_qblk, wpc = math.ceil(NQ / h.i8_split_queries_per_blk(rsplit)), 1
+            n_qblk, wpc = math.ceil(NQ / h.i8_split_queries_per_blk(rsplit, self.dim)), 1
         else:
             n_qblk, wpc = math.ceil(NQ / h.i8_queries_per_blk(rsplit)), h.i8_wgs_per_cu()
         n_rblk = max(1, min(math.ceil(n / (tr * 16)), max(1, round(n_cus * wpc / n_qblk))))
@@ -1419,7 +1455,7 @@ class HbmIndexShard:
                             q8.data_ptr(), NQ, thr.data_ptr(), cs.data_ptr(), ci.data_ptr(),
                             cnt.data_ptr(), cap, self.scan_xcd, st, rsplit, skip=skip,
                             dim=self.dim, heavy=ctx["heavy"], sq=ctx["sq"].data_ptr(), gate=gate,
-                            gate_want=want)
+                            gate_want=want, zero_cnt=0)
         if m4 is not None and self.img_mx4 is not None:
             # (runs: the device counter of searches whose first tier was this scan)
             runs = 0

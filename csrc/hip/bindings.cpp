@@ -89,7 +89,7 @@ int symb_index_scan_i8(const void* X8, const float* sx, int n_valid, int alloc_r
                        int rows_per_blk, int n_rblk, const void* Q8, int NQ, const float* thr,
                        float* cand_s, int* cand_i, int* cand_n, int cap, int xcd, hipStream_t st,
                        int rsplit, const int* skip, int dim, int heavy, const float* sq, int form,
-                       const int* gate, int gate_want);
+                       const int* gate, int gate_want, int zero_cnt);
 int symb_quant_rows_mx4(const void* X, int n, int dim, void* X4, void* SC, float* bounds,
                         float* margin, hipStream_t st);
 int symb_mx4_select(int NQ, const float* T, const float* margin4, const float* margin8,
@@ -120,7 +120,7 @@ int symb_prefill_candidates(int NQ, int r_lo, int n, int* cand_i, int* cand_n, i
                             hipStream_t st);
 int symb_quant_stream_mx4(const void* X, int r0, const int* rows, int n, int dim, void* img,
                           void* Xq, void* QS, float* bounds, float* margin, hipStream_t st);
-int symb_i8_split_queries_per_blk(int rsplit);
+int symb_i8_split_queries_per_blk(int rsplit, int dim);
 int symb_mx4_config(int tile_rows);
 int symb_mx4_tile_rows();
 int symb_quant_rows_split(const float* X, int n, int dim, void* X8, float* sx, float* bounds,
@@ -596,8 +596,9 @@ PYBIND11_MODULE(_hip, m) {
   m.def("mx4_config", [](int tile_rows) { check(symb_mx4_config(tile_rows), "mx4_config"); },
         py::arg("tile_rows"));
   m.def("mx4_tile_rows", []() { return symb_mx4_tile_rows(); });
-  m.def("i8_split_queries_per_blk", [](int rsplit) { return symb_i8_split_queries_per_blk(rsplit); },
-        py::arg("rsplit") = 2);
+  m.def("i8_split_queries_per_blk",
+        [](int rsplit, int dim) { return symb_i8_split_queries_per_blk(rsplit, dim); },
+        py::arg("rsplit") = 2, py::arg("dim") = 384);
   m.def("quant_rows_split", [](uptr X, int n, int dim, uptr X8, uptr sx, uptr bounds, uptr margin,
                                uptr st) {
     check(symb_quant_rows_split(P<const float>(X), n, dim, P<void>(X8), P<float>(sx),
@@ -609,19 +610,21 @@ PYBIND11_MODULE(_hip, m) {
   m.def("index_scan_i8", [](uptr X8, uptr sx, int n_valid, int alloc_rows, int rows_per_blk,
                             int n_rblk, uptr Q8, int NQ, uptr thr, uptr cand_s, uptr cand_i,
                             uptr cand_n, int cap, int xcd, uptr st, int rsplit, uptr skip, int dim,
-                            int heavy, uptr sq, int form, uptr gate, int gate_want) {
+                            int heavy, uptr sq, int form, uptr gate, int gate_want,
+                            int zero_cnt) {
     check(symb_index_scan_i8(P<void>(X8), P<const float>(sx), n_valid, alloc_rows, rows_per_blk,
                              n_rblk,
                              P<void>(Q8), NQ, P<const float>(thr), P<float>(cand_s), P<int>(cand_i),
                              P<int>(cand_n), cap, xcd, S(st), rsplit, P<const int>(skip), dim,
-                             heavy, P<const float>(sq), form, P<const int>(gate), gate_want),
+                             heavy, P<const float>(sq), form, P<const int>(gate), gate_want,
+                             zero_cnt),
           "index_scan_i8");
   }, py::arg("X8"), py::arg("sx"), py::arg("n_valid"), py::arg("alloc_rows"),
      py::arg("rows_per_blk"), py::arg("n_rblk"), py::arg("Q8"), py::arg("NQ"), py::arg("thr"),
      py::arg("cand_s"), py::arg("cand_i"), py::arg("cand_n"), py::arg("cap"), py::arg("xcd"),
      py::arg("stream"), py::arg("rsplit"), py::arg("skip") = 0, py::arg("dim") = 384,
      py::arg("heavy") = 0, py::arg("sq") = 0, py::arg("form") = 0, py::arg("gate") = 0,
-     py::arg("gate_want") = 0);
+     py::arg("gate_want") = 0, py::arg("zero_cnt") = 1);
   m.def("stream_rec_bytes", [](int dim, int form) { return symb_stream_rec_bytes(dim, form); },
         py::arg("dim"), py::arg("form"));
   m.def("stream_config", [](int abl) { check(symb_stream_config(abl), "stream_config"); },

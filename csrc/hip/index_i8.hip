@@ -45,7 +45,11 @@ constexpr int PIECE = 1024;
 // registers leave no room for a 6-slot fragment ring.
 // HK > 0: the SPLIT image (see "split image" below): the first 32 * HK dims of each (rotated) row
 // as fp16, HK v_mfma_f32_16x16x32_f16 k-steps of 64 bytes, then the other D - 32 * HK dims as
-// int8 -- RB = 448 bytes per 384-wide row.  Only the fused two-sub-tile chains run it.
+// int8 -- RB = 448 bytes per 384-wide row, 832 (13 k-steps) per 768-wide one.  Only the fused
+// two-sub-tile chains run it.
+// SETS: 16-query sets per wave.  4, except the 768-wide split image: its 4 x 13 x 4 = 208 query
+// registers leave no room for two accumulator sets and a fragment ring in a 256-register wave
+// (profiles/r6_768/), so a wave holds 2 sets (104 registers) and a workgroup half the queries.
 // HK = MX4 (4): the MX-fp4 image (see "MX-fp4 image" below): every 32-dim block of a row as OCP
 // e2m1 nibbles with a power-of-two block scale, 3 v_mfma_scale_f32_16x16x128_f8f6f4 k-steps of 64
 // bytes -- RB = 192 bytes per 384-wide row, plus 16 bytes of block scales in a side array.
@@ -55,9 +59,10 @@ template <int D, int HK = 0> struct I8Dim {
   static constexpr int RB = NKS * 64;            // image bytes per row
   static constexpr int PF = HK ? NKS - 1 : (D == 384 ? 5 : 3);
   static constexpr int R = PF + 1;
+  static constexpr int SETS = (D == 768 && HK == 2) ? 2 : i8s::SETS;
   static_assert(D == 384 || D == 768, "int8 scan row width");
-  static_assert(HK == 0 || (D == 384 && (HK == 2 || HK == MX4)),
-                "split image: 64 fp16 + 320 int8 dims; MX-fp4 image: 384 dims");
+  static_assert(HK == 0 || HK == 2 || (D == 384 && HK == MX4),
+                "split image: 64 fp16 + D - 64 int8 dims; MX-fp4 image: 384 dims");
   static_assert(NKS % R == 0, "cross-chain prefetch: fragment j of the next chain uses slot j % R");
 };
 
@@ -68,6 +73,11 @@ template <int D, int HK = 0> struct I8Dim {
 // prologue and DMA burst fall under the other's MFMAs instead of in lockstep with them.
 // Split image (HK = 2): 28 KiB tiles = 28 pieces over 8 waves, so waves 0-3 carry 4 pieces and
 // waves 4-7 three (FULLW); a 5-deep ring still fits (156 KiB with the stages).
+// Split image at D = 768: 832-byte rows, so a 64-row tile is 52 KiB = 52 pieces (waves 0-3 carry
+// 7, waves 4-7 six) and a 3-deep ring of them does not fit: a 2-deep ring (120 KiB with the
+// stages), the next tile loading under the current one's chains.  32-row tiles in a 5-deep ring
+// (twice the barriers per row) measured 2.8 % slower at 256 queries per workgroup
+// (profiles/r7_split768/).
 template <int D, int TR_, int WV_ = 8, int HK = 0> struct Geo {
   static constexpr int TR = TR_;
   static constexpr int WV = WV_;
@@ -85,6 +95,7 @@ template <int D, int TR_, int WV_ = 8, int HK = 0> struct Geo {
   static constexpr int STAGE_BYTES = STW * 10;
   // (MX4: 12 KiB tiles, an 8-deep ring keeps ~84 KiB in flight like the int8 5-deep ring)
   static constexpr int NS = WV == 4 ? 3
+                            : (D == 768 && HK == 2) ? 2
                             : HK == MX4 ? (TILE_BYTES <= 12 * 1024 ? 8 : 5)
                             : (TILE_BYTES <= 24 * 1024 ||
                                (HK && 5 * (TILE_BYTES + SC_BYTES) + WV * STAGE_BYTES <= 160 * 1024))
@@ -199,14 +210,14 @@ __device__ __forceinline__ void i8_lgkm2s(i32x4& v0, i32x4& v1, float& t0, float
 // finds them in registers
 template <int D, int KS, int DMA_PIECES, int DE, int HK = 0>
 struct I8Chain2 {
-  static constexpr int NKS = I8Dim<D, HK>::NKS;
+  static constexpr int NKS = I8Dim<D, HK>::NKS, SETS = I8Dim<D, HK>::SETS;
   template <class Dma>
-  __device__ __forceinline__ static void run(i32x4 (&acc)[2][i8s::SETS],
-                                             f32x4 (&accf)[HK ? 2 : 1][i8s::SETS],
+  __device__ __forceinline__ static void run(i32x4 (&acc)[2][SETS],
+                                             f32x4 (&accf)[HK ? 2 : 1][SETS],
                                              i32x4 (&a)[i8s::R2][2],
-                                             const i32x4 (&qf)[i8s::SETS][NKS],
+                                             const i32x4 (&qf)[SETS][NKS],
                                              uint32_t base, const Dma& dma, f32x4& t0, f32x4& t1,
-                                             const float (&qsc)[i8s::SETS], float& r0, float& r1) {
+                                             const float (&qsc)[SETS], float& r0, float& r1) {
     using namespace i8s;
     if constexpr (DMA_PIECES > 0 && KS % DE == 0 && KS / DE < DMA_PIECES) dma(KS / DE);
     constexpr int steps = (NKS - KS < PF2) ? (NKS - KS) : PF2;   // k-steps in flight, this one too
@@ -285,6 +296,7 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void index_scan_i8_kernel(
   using namespace i8s;
   using G = Geo<D, TRK, WV, HK>;
   constexpr int NKS = G::NKS, RB = G::RB;
+  constexpr int SETS = I8Dim<D, HK>::SETS;   // (hides i8s::SETS: 2 for the 768-wide split image)
   constexpr int TR = G::TR, NSUB = G::NSUB, NS = G::NS, TILE_BYTES = G::TILE_BYTES;
   constexpr int LOADS = G::LOADS, SC_BYTES = G::SC_BYTES, STW = G::STW;
   constexpr int STAGE_BYTES = G::STAGE_BYTES;
@@ -528,8 +540,9 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void index_scan_i8_kernel(
   // cross-chain prefetch and measured slower, 10.55 -> 11.15 ms at 12.5M x 2048)
   // (D = 768: single-sub-tile chains -- the fused pair's extra fragment and accumulator
   // registers do not fit beside 192 query registers)
-  // (the split image always runs fused chains)
-  constexpr bool FUSE = D == 384 && NSW % 2 == 0 && (RSPLIT == 2 || TRK == 128 || HK > 0);
+  // (the split image always runs fused chains, at D = 768 too: 2 query sets per wave there)
+  constexpr bool FUSE = (D == 384 || HK == 2) && NSW % 2 == 0 &&
+                        (RSPLIT == 2 || TRK == 128 || HK > 0);
   static_assert(HK == 0 || FUSE, "split image: fused chains only");
   constexpr int NG = FUSE ? NSW / 2 : 1;   // fused chains per wave per tile
   i32x4 a2[FUSE ? R2 : 1][2];
@@ -1369,7 +1382,7 @@ static int launch_i8(const void* X8, const float* sx, int n_valid, int rows_per_
                      const void* Q8, int NQ, const float* thr, float* cand_s, int* cand_i,
                      int* cand_n, int cap, int xcd, hipStream_t st, const int* skip,
                      const float* sq = nullptr, const int* gate = nullptr, int gate_want = 0) {
-  constexpr int qpb = WV / RSPLIT * 16 * i8s::SETS;
+  constexpr int qpb = WV / RSPLIT * 16 * I8Dim<D, HK>::SETS;
   const int n_qblk = (NQ + qpb - 1) / qpb;
   constexpr int lds = Geo<D, TRK, WV, HK>::LDS_BYTES;
   auto go = [&](auto kern) {
@@ -1386,29 +1399,35 @@ static int launch_i8(const void* X8, const float* sx, int n_valid, int rows_per_
 // Tile rows the D-wide scan runs with (the 128-row and 4-wave forms are D = 384 knobs; the split
 // image runs 64-row tiles, 8 waves).
 int symb_i8_tile_rows_for(int dim, int heavy) { return dim == 384 && !heavy ? g_i8_tr : 64; }
-int symb_i8_split_queries_per_blk(int rsplit) { return i8s::WAVES / rsplit * 16 * i8s::SETS; }
+// queries per workgroup of the split image's scan: 4 query sets per wave at 384 (256 / 512 for
+// rsplit 2 / 1), 2 at 768 (128 / 256)
+int symb_i8_split_queries_per_blk(int rsplit, int dim) {
+  return i8s::WAVES / rsplit * 16 * (dim == 768 ? I8Dim<768, 2>::SETS : I8Dim<384, 2>::SETS);
+}
 
 // rows_per_blk % tile rows == 0, n_rblk * rows_per_blk >= n_valid; X8 / sx hold alloc_rows
 // rows, which must cover n_valid rounded up to a whole tile (the DMA reads whole tiles).
-// rsplit 2 = 256 queries per workgroup, 1 = 512.  dim: 384 or 768.  heavy = 64: the split image
-// (448-byte rows and queries, quant_rows_split), sq = the queries' int8 scales; 0: plain int8.
+// rsplit 2 = 256 queries per workgroup, 1 = 512 (the 768-wide split image: 128 / 256,
+// symb_i8_split_queries_per_blk).  dim: 384 or 768.  heavy = 64: the split image (dim + 64-byte
+// rows and queries, quant_rows_split), sq = the queries' int8 scales; 0: plain int8.
 // form: 0 = plain int8 (heavy 0) or split (heavy 64); 1 = the MX-fp4 image (sx = the rows'
 // block scales, sq = the queries'; quant_rows_mx4).  gate / gate_want: the launch runs only if
-// *gate == gate_want (nullptr: always); cand_n is zeroed only by an ungated launch.
+// *gate == gate_want (nullptr: always); cand_n is zeroed only by an ungated launch with zero_cnt
+// (0: the caller cleared the counters itself and may have pre-filled candidates).
 int symb_index_scan_i8(const void* X8, const float* sx, int n_valid, int alloc_rows,
                        int rows_per_blk, int n_rblk, const void* Q8, int NQ, const float* thr,
                        float* cand_s, int* cand_i, int* cand_n, int cap, int xcd, hipStream_t st,
                        int rsplit, const int* skip, int dim, int heavy, const float* sq, int form,
-                       const int* gate, int gate_want) {
+                       const int* gate, int gate_want, int zero_cnt) {
   if (NQ <= 0) return 0;
   if (dim != 384 && dim != 768) return -1;
-  if (heavy != 0 && (heavy != 64 || dim != 384 || sq == nullptr)) return -1;
+  if (heavy != 0 && (heavy != 64 || sq == nullptr)) return -1;
   if (form != 0 && (form != 1 || heavy != 0 || dim != 384 || sq == nullptr)) return -1;
   const int tr = form ? (rsplit == 2 ? g_mx4_tr : 64) : symb_i8_tile_rows_for(dim, heavy);
   if (rows_per_blk % tr || n_rblk <= 0 || thr == nullptr || cap <= 0 || n_valid <= 0) return -1;
   if ((long long)n_rblk * rows_per_blk < n_valid) return -1;
   if ((long long)(n_valid + tr - 1) / tr * tr > alloc_rows) return -1;   // a tile past the buffer
-  if (gate == nullptr) {
+  if (gate == nullptr && zero_cnt) {
     hipError_t e = hipMemsetAsync(cand_n, 0, sizeof(int) * (size_t)NQ, st);
     if (e != hipSuccess) return (int)e;
   }
@@ -1426,6 +1445,13 @@ int symb_index_scan_i8(const void* X8, const float* sx, int n_valid, int alloc_r
                        : launch_i8<384, 1, 64, 8, MX4>(X8, sx, n_valid, rows_per_blk, n_rblk, Q8,
                                                        NQ, thr, cand_s, cand_i, cand_n, cap, xcd,
                                                        st, skip, sq, gate, gate_want);
+  if (heavy && dim == 768)
+    return rsplit == 2 ? launch_i8<768, 2, 64, 8, 2>(X8, sx, n_valid, rows_per_blk, n_rblk, Q8, NQ,
+                                                     thr, cand_s, cand_i, cand_n, cap, xcd, st,
+                                                     skip, sq, gate, gate_want)
+                       : launch_i8<768, 1, 64, 8, 2>(X8, sx, n_valid, rows_per_blk, n_rblk, Q8, NQ,
+                                                     thr, cand_s, cand_i, cand_n, cap, xcd, st,
+                                                     skip, sq, gate, gate_want);
   if (heavy)
     return rsplit == 2 ? launch_i8<384, 2, 64, 8, 2>(X8, sx, n_valid, rows_per_blk, n_rblk, Q8, NQ,
                                                      thr, cand_s, cand_i, cand_n, cap, xcd, st,
@@ -1489,9 +1515,13 @@ int symb_quant_rows_i8(const void* X, int n, int dim, void* X8, float* sx, float
 int symb_quant_rows_split(const float* X, int n, int dim, void* X8, float* sx, float* bounds,
                           float* margin, hipStream_t st) {
   if (n <= 0) return 0;
-  if (dim != 384 || bounds == nullptr) return -1;
-  hipLaunchKernelGGL((quant_rows_split_kernel<384, 64>), dim3((n + 3) / 4), dim3(256), 0, st, X, n,
-                     (int8_t*)X8, sx, bounds, margin);
+  if ((dim != 384 && dim != 768) || bounds == nullptr) return -1;
+  if (dim == 768)   // (11 trailing dims per lane)
+    hipLaunchKernelGGL((quant_rows_split_kernel<768, 64>), dim3((n + 3) / 4), dim3(256), 0, st, X,
+                       n, (int8_t*)X8, sx, bounds, margin);
+  else
+    hipLaunchKernelGGL((quant_rows_split_kernel<384, 64>), dim3((n + 3) / 4), dim3(256), 0, st, X,
+                       n, (int8_t*)X8, sx, bounds, margin);
   return (int)hipGetLastError();
 }
 
