@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""Filtered search (exact top-k under a row mask, csrc/hip/index_filter.hip) against what a caller
+could do before it, on one bf16 shard of random unit rows with held-out random queries.
+
+Per mask, in alternated rounds on the same shard (one JSON line per mask and variant):
+
+  filtered_seed    shard.search(q, k, allow=mask), seed pass on
+  filtered_noseed  ... seed pass off
+  gather_scan      index_select of the allowed rows, then the unfiltered list scan (_scan) over
+                   the copy, ids mapped back (skipped where the copy does not fit)
+  search           the unfiltered shard.search(q, k)            (yardstick, mask-independent)
+  plain_scan       the unfiltered, unseeded list scan (_scan)  (yardstick, mask-independent)
+
+Masks: all ones; uniform random bits; "documents" = runs of 200 consecutive rows.  The RowMask
+(packed bits + live-tile list) and the gather's row list are built once per mask, outside the
+timed loops; ``mask_ms`` is that one-off cost of the RowMask.
+
+    python benchmarks/filter_bench.py [--rows 100000000] [--dim 384] [--nq 256] [--k 10]
+        [--masks ones,u50,u10,u1,d10,d1,d0.1] [--rounds 3] [--iters 5] [--out FILE]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+DOC_ROWS = 200
+
+
+def build_allow(name: str, n: int, dev, seed: int) -> torch.Tensor:
+    g = torch.Generator(device=dev).manual_seed(seed)
+    if name == "ones":
+        return torch.ones(n, dtype=torch.bool, device=dev)
+    share = float(name[1:]) / 100.0
+    if name[0] == "u":
+        return torch.rand(n, device=dev, generator=g) < share
+    if name[0] == "d":
+        n_docs = max(1, round(share * n / DOC_ROWS))
+        starts = torch.randint(0, n - DOC_ROWS, (n_docs,), device=dev, generator=g)
+        edge = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        one = torch.ones(n_docs, dtype=torch.int32, device=dev)
+        edge.index_add_(0, starts, one)
+        edge.index_add_(0, starts + DOC_ROWS, -one)
+        return torch.cumsum(edge[:n], 0, dtype=torch.int32) > 0
+    raise ValueError(f"unknown mask {name!r}")
+
+
+def timed(fn, iters: int) -> float:
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e3
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=100_000_000)
+    ap.add_argument("--dim", type=int, default=384)
+    ap.add_argument("--nq", type=int, default=256)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--masks", default="ones,u50,u10,u1,d10,d1,d0.1")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("filter_bench needs the GPU: nothing here is measured without one")
+    from codename_symbiont_amd.index.shard import TILE_ROWS, HbmIndexShard
+
+    dev = torch.device("cuda")
+    n, k = a.rows, a.k
+    kmax = 16 if k <= 16 else 32
+    shard = HbmIndexShard(a.dim, n, device=dev)
+    shard.fill_random(n, seed=1)
+    g = torch.Generator(device=dev).manual_seed(77)      # held out: not rows of the shard
+    q = torch.nn.functional.normalize(torch.randn(a.nq, a.dim, device=dev, generator=g),
+                                      dim=-1).bfloat16()
+    out = open(a.out, "a") if a.out else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+    base = {"bench": "filter_bench", "rows": n, "dim": a.dim, "nq": a.nq, "k": k,
+            "rounds": a.rounds, "iters": a.iters}
+    for mi, name in enumerate(a.masks.split(",")):
+        allow = build_allow(name, n, dev, 100 + mi)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        mask = shard.make_mask(allow)
+        torch.cuda.synchronize()
+        mask_ms = (time.perf_counter() - t0) * 1e3
+        n_allowed, n_live = int(allow.sum()), int(mask.n_live)
+        info = dict(base, mask=name, allowed=n_allowed, allowed_share=round(n_allowed / n, 5),
+                    live_tiles=n_live, live_share=round(n_live / ((n + 63) // 64), 5),
+                    mask_ms=round(mask_ms, 3))
+        idx = torch.nonzero(allow).flatten()
+        del allow
+        m = idx.numel()
+        m_pad = (m + TILE_ROWS - 1) // TILE_ROWS * TILE_ROWS
+        free, _ = torch.cuda.mem_get_info(dev)
+        gather_ok = m > 0 and m_pad * a.dim * 2 < free - (8 << 30)
+        sub = torch.zeros(m_pad, a.dim, dtype=torch.bfloat16, device=dev) if gather_ok else None
+
+        def filtered(seed):
+            shard.filter_seed = seed
+            return shard.search(q, k, allow=mask)
+
+        def gather():
+            torch.index_select(shard.rows, 0, idx, out=sub[:m])
+            s, r = shard._scan(m, q, kmax, k, None, None, rows=sub)
+            return s, idx[r.long().clamp_min(0)]
+
+        variants = {"filtered_seed": lambda: filtered(True),
+                    "filtered_noseed": lambda: filtered(False),
+                    "search": lambda: shard.search(q, k),
+                    "plain_scan": lambda: shard._scan(n, q, kmax, k, None, None)}
+        if gather_ok:
+            variants["gather_scan"] = gather
+        # results first (also the warm-up of every shape): seed on == seed off == gather
+        res = {v: fn() for v, fn in variants.items()}
+        torch.cuda.synchronize()
+        same_seed = bool(torch.equal(res["filtered_seed"][0], res["filtered_noseed"][0])
+                         and torch.equal(res["filtered_seed"][1], res["filtered_noseed"][1]))
+        same_gather = None
+        if gather_ok:
+            same_gather = bool(torch.equal(res["filtered_seed"][0], res["gather_scan"][0]))
+        del res
+        times = {v: [] for v in variants}
+        for _ in range(a.rounds):            # alternated: every variant once per round
+            for v, fn in variants.items():
+                times[v].append(timed(fn, a.iters))
+        for v, ts in times.items():
+            emit(dict(info, variant=v, ms=round(statistics.median(ts), 3),
+                      ms_min=round(min(ts), 3), ms_max=round(max(ts), 3),
+                      seed_on_equals_off=same_seed, scores_equal_gather=same_gather))
+        del sub, idx, mask
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

@@ -51,7 +51,13 @@ class PayloadStore:
     often the bulk of a 100M-row shard) cost nothing here and decode to the reference's defaults
     ("" / 0, main.rs:337-390).  A dense layout kept 7 Python lists of n slots: 560 MB of list
     pointers per 10M rows, traversed by every full GC pass of the service process (the e2e
-    benchmark's ~100 ms tail)."""
+    benchmark's ~100 ms tail).
+
+    Filtered searches (index/filter.py) need value -> rows for the filterable fields.  That index
+    is built lazily, per field, by the first filter that names the field, and kept current by
+    ``set`` and ``truncate`` from then on: a dict of row sets over 100M payload rows is gigabytes
+    of small objects for the same GC passes to walk, so a store that is never filtered (the
+    service as it runs today) pays nothing for it."""
 
     FIELDS = ("original_document_id", "source_url", "sentence_text", "sentence_order",
               "model_name", "processed_at_ms")
@@ -65,6 +71,35 @@ class PayloadStore:
         # recorded only while a persister tracks this store
         self.track = False
         self.dirty: set[int] = set()
+        # field -> value -> rows, only for fields some filter has named (rows_with)
+        self._by_value: dict[str, dict[object, set[int]]] = {}
+
+    def _field_value(self, t: tuple, field: str):
+        v = t[self.FIELDS.index(field)]
+        return "" if v is None else v
+
+    def rows_with(self, field: str, value) -> set[int]:
+        """Rows whose stored payload has ``field`` == ``value`` (the field's index is built on
+        its first use; do not modify the returned set)."""
+        idx = self._by_value.get(field)
+        if idx is None:
+            idx = {}
+            for row, t in self.fields.items():
+                idx.setdefault(self._field_value(t, field), set()).add(row)
+            self._by_value[field] = idx
+        return idx.get(value, set())
+
+    def _unindex(self, row: int) -> None:
+        t = self.fields.get(row)
+        if t is None:
+            return
+        for field, idx in self._by_value.items():
+            v = self._field_value(t, field)
+            rows = idx.get(v)
+            if rows is not None:
+                rows.discard(row)
+                if not rows:
+                    del idx[v]
 
     def __len__(self):
         return self.n
@@ -81,8 +116,12 @@ class PayloadStore:
         if point_id is not None:
             self.point_ids[row] = point_id
             self.id_to_row[point_id] = row
+        if self._by_value:
+            self._unindex(row)
         if payload is not None:
-            self.fields[row] = tuple(getattr(payload, f) for f in self.FIELDS)
+            t = self.fields[row] = tuple(getattr(payload, f) for f in self.FIELDS)
+            for field, idx in self._by_value.items():
+                idx.setdefault(self._field_value(t, field), set()).add(row)
         else:
             self.fields.pop(row, None)
         if self.track:
@@ -108,6 +147,8 @@ class PayloadStore:
             if self.id_to_row.get(pid) == r:
                 del self.id_to_row[pid]
         for r in [r for r in self.fields if r >= n]:
+            if self._by_value:
+                self._unindex(r)
             del self.fields[r]
         self.dirty = {r for r in self.dirty if r < n}
         self.n = n
@@ -152,6 +193,56 @@ STREAM_SUB = 32                         # rows per sub-tile record of the stream
 # ... where the int8 tier runs the LDS-ring scan (index_i8.hip) beside the stream fp4 tier: 100M x
 # 768 held-out 21.6 ms against 25.4 ms for the LDS-query stream form (profiles/r6_768/)
 I8_RING_DIMS = (768,)
+
+
+FILTER_DIMS = (384, 768, 1024)          # ... the masked list scan (index_filter.hip)
+
+
+def _pack_bits(allow: torch.Tensor, n_words: int) -> torch.Tensor:
+    """bool [n <= 64 n_words] -> uint8 [8 n_words]: bit r % 8 of byte r // 8 = allow[r]
+    (numpy.packbits(bitorder="little")), zero-padded to whole 64-bit words."""
+    pad = torch.zeros(n_words * 64, dtype=torch.uint8, device=allow.device)
+    pad[:allow.numel()] = allow
+    w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=allow.device)
+    return (pad.view(-1, 8) * w).sum(1, dtype=torch.uint8)
+
+
+def _unpack_bits(packed: torch.Tensor) -> torch.Tensor:
+    """uint8 [m] -> bool [8 m] (the inverse of _pack_bits)."""
+    sh = torch.arange(8, dtype=torch.uint8, device=packed.device)
+    return ((packed[:, None] >> sh) & 1).bool().reshape(-1)
+
+
+class RowMask:
+    """The rows of one shard a search may return, built once by ``HbmIndexShard.make_mask`` and
+    reused by every search under the same filter.
+
+    ``bits``: packed uint8 on the shard's device, one bit per row, little-endian within a byte,
+    whole 64-bit words; bits at or past ``visible`` are clear.  ``visible``: the shard's visible
+    rows when the mask was built -- rows appended later are disallowed under it.  ``tiles`` /
+    ``n_live`` (shards the masked scan serves, else None): the ascending 64-row tiles that hold
+    an allowed row and their count, device tensors from ``filter_tiles``."""
+
+    __slots__ = ("bits", "visible", "tiles", "n_live")
+
+    def __init__(self, bits: torch.Tensor, visible: int, tiles=None, n_live=None):
+        self.bits, self.visible, self.tiles, self.n_live = bits, int(visible), tiles, n_live
+
+    @property
+    def words(self) -> torch.Tensor:
+        return self.bits.view(torch.int64)
+
+    def bool_rows(self, s: int, e: int) -> torch.Tensor:
+        """bool [e - s]: rows [s, e) allowed (rows past the mask are not)."""
+        b0 = s // 8
+        u = _unpack_bits(self.bits[b0:(e + 7) // 8])[s - b0 * 8:e - b0 * 8]
+        if u.numel() < e - s:
+            u = torch.cat([u, torch.zeros(e - s - u.numel(), dtype=torch.bool, device=u.device)])
+        return u
+
+    def count(self) -> int:
+        """Allowed rows (reads the device: diagnostics and tests)."""
+        return int(_unpack_bits(self.bits).sum())
 
 
 class HbmIndexShard:
@@ -269,6 +360,9 @@ class HbmIndexShard:
         self.prepass_min_tiles = 1
         self.scan_aux = -1   # index-stream cache policy (-1 = auto: non-temporal when read once)
         self.seed_threshold = True  # sample pre-pass seeds per-query top-k thresholds
+        # masked search (_search_filtered): a stride-64 pass over the live tiles first, whose k-th
+        # best allowed score seeds the full pass's thresholds (FILTER_SEED_DEFAULT has the A/B)
+        self.filter_seed = self.FILTER_SEED_DEFAULT
         self.scan_variant = 0        # fp8 scan ring geometry (0 = default)
         # > 256 queries: put the query blocks of each row block on one XCD (row stream shared
         # through that XCD's L2 instead of re-read from HBM once per query block)
@@ -860,10 +954,15 @@ class HbmIndexShard:
         self.publish()
 
     # ------------------------------------------------------------------ search
-    def search(self, q_unit: torch.Tensor, k: int, n_cus: int | None = None):
+    def search(self, q_unit: torch.Tensor, k: int, n_cus: int | None = None, *, allow=None):
         """Top-k cosine over this shard for unit bf16 queries [NQ, D].
 
+        ``allow`` (a ``RowMask``, or anything ``make_mask`` takes): only those rows may be
+        returned; the search is exact over them (_search_masked).
+
         Returns (scores f32 [NQ, k], rows int32 [NQ, k]); missing slots are (-inf, -1)."""
+        if allow is not None:
+            return self._search_masked(q_unit, k, n_cus, allow)
         NQ = q_unit.shape[0]
         k = int(k)
         if NQ == 0 or k <= 0:
@@ -891,11 +990,15 @@ class HbmIndexShard:
             out_s.mul_(1.0 / (FP8_SCALE * FP8_SCALE))
         return out_s, out_i
 
-    def search_begin(self, q_unit: torch.Tensor, k: int, n_cus: int | None = None) -> dict:
+    def search_begin(self, q_unit: torch.Tensor, k: int, n_cus: int | None = None, *,
+                     allow=None) -> dict:
         """First half of ``search`` for a pipelined caller: on the pruned path, the query-side
         work (int8 queries, exact sample, thresholds, route) runs now on the current stream and
         ``search_end`` runs the full-shard scan later, possibly on another stream -- the bench
-        overlaps batch i + 1's begin with batch i's scan.  Any other path runs whole here."""
+        overlaps batch i + 1's begin with batch i's scan.  Any other path (a masked search
+        among them) runs whole here."""
+        if allow is not None:
+            return {"full": self.search(q_unit, k, n_cus, allow=allow)}
         q = q_unit.to(torch.bfloat16).contiguous()
         k = int(k)
         if (self.device.type == "cuda" and self.prune and not self.prefilter and 0 < k <= 16
@@ -910,6 +1013,120 @@ class HbmIndexShard:
         if "full" in ctx:
             return ctx["full"]
         return self._pruned_end(ctx)
+
+    # ------------------------------------------------------------------ search under a row mask
+    # seed pass of the masked scan on by default?  (profiles/r8_filter/ has the A/B)
+    FILTER_SEED_DEFAULT = True
+    FILTER_SEED_STRIDE = 64
+    # row-block floor of the masked scan's grid, in 64-row tiles (smaller than the unmasked list
+    # scan's 16: under a sparse mask most of a block's tiles are dead; not tuned)
+    FILTER_MIN_TILES = 4
+
+    def make_mask(self, allow) -> RowMask:
+        """Rows a search may return -> ``RowMask`` at the rows visible now.  ``allow`` is one of
+
+        * a bool tensor / array of length up to ``visible`` (shorter: the rest is disallowed);
+        * a list / int tensor / int array of row numbers (each in [0, visible));
+        * the packed bits themselves: ``bytes`` or a uint8 tensor / array, bit r % 8 of byte
+          r // 8 = row r (numpy.packbits(bitorder="little")); bits at or past ``visible`` are
+          cleared.
+
+        A device tensor is packed on the device without a host sync (row numbers outside the
+        shard are then dropped instead of refused).  On a GPU shard the masked scan serves, the
+        live-tile list is built here, once (``filter_tiles``)."""
+        if isinstance(allow, RowMask):
+            return allow
+        v, dev = self.visible, self.device
+        if isinstance(allow, (bytes, bytearray, memoryview)):
+            allow = torch.frombuffer(bytearray(allow), dtype=torch.uint8)
+        on_dev = isinstance(allow, torch.Tensor) and allow.device.type != "cpu"
+        if isinstance(allow, (list, tuple, range)):
+            allow = torch.tensor(list(allow), dtype=torch.int64)
+        a = torch.as_tensor(allow).flatten()
+        if a.dtype == torch.bool:
+            if a.numel() > v:
+                raise ValueError(f"make_mask: {a.numel()} mask entries for {v} visible rows")
+            ok = a.to(dev)
+        elif a.dtype == torch.uint8:
+            ok = _unpack_bits(a.to(dev))[:v]
+        elif a.dtype in (torch.int16, torch.int32, torch.int64):
+            if not on_dev and a.numel() and (int(a.min()) < 0 or int(a.max()) >= v):
+                raise IndexError(f"make_mask: row outside the {v} visible rows")
+            r = a.to(dev, torch.int64)
+            hit = torch.zeros(v + 1, dtype=torch.bool, device=dev)
+            hit[torch.where((r >= 0) & (r < v), r, torch.full_like(r, v))] = True
+            ok = hit[:v]
+        else:
+            raise TypeError(f"make_mask: bool mask, int rows or packed uint8 bits, got {a.dtype}")
+        bits = _pack_bits(ok, max(1, (v + TILE_ROWS - 1) // TILE_ROWS))
+        tiles = n_live = None
+        if dev.type == "cuda" and self.dtype == "bf16" and self.dim in FILTER_DIMS:
+            from ..ops.kernels import filter_tiles
+
+            tiles, n_live = filter_tiles(bits.view(torch.int64), v)
+        return RowMask(bits, v, tiles, n_live)
+
+    def _search_masked(self, q_unit, k: int, n_cus, allow):
+        """``search`` under a row mask, exact over the allowed bf16 rows.  A GPU bf16 shard of a
+        width in FILTER_DIMS at k <= 32 takes the masked list scan; everything else (CPU and fp8
+        shards, k > 32, other widths) the chunked matmul with the score block masked.  The cheap
+        routes of the unmasked search do not apply: their thresholds come from a sample of ALL
+        rows, which is no lower bound on the k-th allowed score."""
+        NQ = q_unit.shape[0]
+        k = int(k)
+        if NQ == 0 or k <= 0:
+            return (torch.empty(NQ, max(k, 0), device=self.device),
+                    torch.empty(NQ, max(k, 0), dtype=torch.int32, device=self.device))
+        mask = self.make_mask(allow)
+        if mask.bits.device != self.device:
+            raise ValueError(f"RowMask on {mask.bits.device}, shard on {self.device}")
+        if (self.device.type == "cuda" and self.dtype == "bf16" and self.dim in FILTER_DIMS
+                and k <= 32 and mask.tiles is not None):
+            return self._search_filtered(q_unit.to(torch.bfloat16).contiguous(), k, mask, n_cus)
+        return self._search_matmul(q_unit, k, mask=mask)
+
+    def _search_filtered(self, q_unit, k: int, mask: RowMask, n_cus):
+        """The masked list scan (index_filter.hip) + merge.  The grid and the candidate
+        workspace are sized as if every tile were live; the kernel reads the live count on the
+        device.  ``filter_seed``: a first pass over every FILTER_SEED_STRIDE-th live tile of each
+        workgroup's slice sees allowed rows only, so its k-th best is a lower bound on the final
+        k-th allowed score (-inf where it found fewer than k rows); the full pass starts from
+        it.  Exact either way."""
+        from ..ops import kernels as K
+        from ..ops._ext import hip, stream_handle
+
+        h, dev = hip(), self.device
+        NQ = q_unit.shape[0]
+        kmax = 16 if k <= 16 else 32
+        n = min(mask.visible, self.visible)
+        out_s = torch.empty(NQ, k, device=dev)
+        out_i = torch.empty(NQ, k, dtype=torch.int32, device=dev)
+        if n <= 0:
+            return out_s.fill_(-math.inf), out_i.fill_(-1)
+        lists, qpb = h.topk_geometry(self.dim, kmax)
+        n_qblk = math.ceil(NQ / qpb)
+        if n_cus is None:
+            n_cus = self._n_cus()
+        n_rblk = max(1, min(math.ceil(n / (TILE_ROWS * self.FILTER_MIN_TILES)),
+                            max(1, round(n_cus / n_qblk))))
+        ncand = n_rblk * lists * kmax
+        cs = torch.empty(NQ, ncand, device=dev)
+        ci = torch.empty(NQ, ncand, dtype=torch.int32, device=dev)
+        st = stream_handle(dev)
+
+        def one_pass(thr, stride):
+            K.index_scan_filter(self.rows, n, mask.words, mask.tiles, mask.n_live, q_unit, kmax,
+                                n_rblk, cs, ci, thr, stride, self.scan_xcd)
+            h.topk_merge(cs.data_ptr(), ci.data_ptr(), NQ, ncand, kmax, k, out_s.data_ptr(),
+                         out_i.data_ptr(), 0, 0, st, 0)
+
+        thr = None
+        if self.filter_seed:
+            one_pass(None, self.FILTER_SEED_STRIDE)
+            kth = out_s[:, k - 1].contiguous()
+            thr = torch.nextafter(kth, torch.full_like(kth, -math.inf))
+        one_pass(thr, 1)
+        return out_s, out_i
 
     def _search_scan(self, q_unit, k: int, rows, dtype: str, n_cus):
         """Seeded fused scan + merge over ``rows`` (bf16 slab, or e4m3 bytes for dtype fp8)."""
@@ -1669,12 +1886,13 @@ class HbmIndexShard:
                      out_i.data_ptr(), 0, 0, st, gate_p)
         return out_s, out_i
 
-    def _search_matmul(self, q_unit: torch.Tensor, k: int, chunk: int = 1 << 22):
+    def _search_matmul(self, q_unit: torch.Tensor, k: int, chunk: int = 1 << 22, mask=None):
         """Chunked exact fallback (CPU backend, or k > 32 on GPU).  Each chunk's fp32 score block
         stays <= 512 MiB: one GEMM output past 2 GiB came back with its tail unwritten on the
-        GPU stack (benchmarks/diag/gemm_2g.py)."""
+        GPU stack (benchmarks/diag/gemm_2g.py).  ``mask`` (RowMask): disallowed rows score -inf;
+        score column j of a chunk is row s + j, so the chunk takes the mask's rows [s, e)."""
         NQ = q_unit.shape[0]
-        chunk = max(4096, min(chunk, (1 << 27) // max(1, NQ)))
+        chunk = max(min(chunk, 4096), min(chunk, (1 << 27) // max(1, NQ)))
         best_s = torch.full((NQ, k), -math.inf, device=self.device)
         best_i = torch.full((NQ, k), -1, dtype=torch.int64, device=self.device)
         q = q_unit.to(self.device).float()
@@ -1682,6 +1900,8 @@ class HbmIndexShard:
         for s in range(0, n, chunk):
             e = min(n, s + chunk)
             sc = q @ self._rows_f32(s, e).t()
+            if mask is not None:
+                sc.masked_fill_(~mask.bool_rows(s, e)[None, :], -math.inf)
             kk = min(k, e - s)
             ts, ti = torch.topk(sc, kk, dim=1)
             cat_s = torch.cat([best_s, ts], 1)

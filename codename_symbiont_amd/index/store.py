@@ -9,6 +9,7 @@ descending with fewer than k results when the collection is small.
 """
 from __future__ import annotations
 
+import collections
 import logging
 import os
 import threading
@@ -16,6 +17,7 @@ import threading
 import numpy as np
 import torch
 
+from .filter import Filter
 from .persist import ShardPersister, Wal, committed_gen, load_snapshot, wal_files
 from .shard import HbmIndexShard, Payload
 
@@ -85,6 +87,9 @@ class VectorStore:
         self._since_snapshot = 0
         self._lock = threading.Lock()
         self._frag: dict[int, tuple[bytes, bytes]] = {}
+        # RowMasks of recent filters, by filter value (LRU); dropped whole by every upsert: an
+        # overwritten row may have changed documents, an appended one may match
+        self._masks: collections.OrderedDict = collections.OrderedDict()
         # SYMB_SEARCH_PIPELINE (default on, single GPU shard): a search's query-side pre-pass
         # (HbmIndexShard.search_begin) runs on one stream and its full-shard scan (search_end) on
         # another, so with the service's two scans in flight the next burst's pre-pass runs
@@ -148,6 +153,7 @@ class VectorStore:
             out = self.shard.upsert(point_ids, t, payloads)
         for g in out or ():
             self._frag.pop(int(g), None)   # (re)written rows: their cached result JSON is stale
+        self._masks.clear()
         return out
 
     def upsert(self, point_ids: list[str], vecs: np.ndarray, payloads: list[Payload]) -> None:
@@ -227,8 +233,35 @@ class VectorStore:
             job = self._cut_locked()
         self._start(job, background=not wait)
 
-    def search(self, queries: np.ndarray, k: int):
-        """queries f32 [nq, D] (any norm) -> (scores f32 [nq, k'], rows int64 [nq, k']); -1 = empty."""
+    FILTER_CACHE_MAX = 16
+
+    def _mask_for(self, flt: Filter):
+        """The shard's RowMask of a filter: evaluated on the host against the payload store (under
+        the upsert lock: an upsert rewrites the dicts it reads) and cached by the filter's value,
+        so repeated searches under one filter pay neither the evaluation nor the tile list."""
+        if not isinstance(flt, Filter):
+            raise TypeError(f"filter must be an index.filter.Filter, got {type(flt).__name__}")
+        key = flt.key()
+        with self._lock:
+            mask = self._masks.get(key)
+            if mask is None:
+                n = self.shard.visible
+                mask = self.shard.make_mask(flt.evaluate(self.shard.payloads, n))
+                self._masks[key] = mask
+                while len(self._masks) > self.FILTER_CACHE_MAX:
+                    self._masks.popitem(last=False)
+            else:
+                self._masks.move_to_end(key)
+        return mask
+
+    def search(self, queries: np.ndarray, k: int, filter: Filter | None = None):
+        """queries f32 [nq, D] (any norm) -> (scores f32 [nq, k'], rows int64 [nq, k']); -1 = empty.
+
+        ``filter`` (index.filter.Filter): only points that pass may be returned; the search is
+        exact over them, and slots past the passing points are (-inf, -1)."""
+        if filter is not None and self.group is not None:
+            raise ValueError("filtered search is single-shard for now: this store searches a "
+                             "multi-GPU group")
         q = np.asarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None]
@@ -238,8 +271,9 @@ class VectorStore:
         k = int(k)
         if k <= 0 or self.count == 0:
             return np.zeros((q.shape[0], 0), np.float32), np.zeros((q.shape[0], 0), np.int64)
+        kw = {"allow": self._mask_for(filter)} if filter is not None else {}
         if self._streams is not None:
-            return self._search_pipelined(q, k)
+            return self._search_pipelined(q, k, **kw)
         qt = torch.nn.functional.normalize(torch.from_numpy(q).to(self.shard.device), dim=-1)
         qt = qt.to(torch.bfloat16)
         if self.group is not None:
@@ -250,10 +284,10 @@ class VectorStore:
                     e.scores, e.ids = e.scores.float().cpu().numpy(), e.ids.long().cpu().numpy()
                 raise
         else:
-            s, r = self.shard.search(qt, k)
+            s, r = self.shard.search(qt, k, **kw)
         return s.float().cpu().numpy(), r.long().cpu().numpy()
 
-    def _search_pipelined(self, q: np.ndarray, k: int):
+    def _search_pipelined(self, q: np.ndarray, k: int, **kw):
         """search() of a single GPU shard on two streams: pre-pass (begin) on the first, scan
         (end) on the second.  Both order after every write already enqueued on the default
         stream (upserts), and each stream runs its calls in the order they were made, so two
@@ -266,7 +300,7 @@ class VectorStore:
             pre.wait_stream(torch.cuda.default_stream(dev))
             with torch.cuda.stream(pre):
                 qt = torch.nn.functional.normalize(qh, dim=-1).to(torch.bfloat16)
-                ctx = self.shard.search_begin(qt, k)
+                ctx = self.shard.search_begin(qt, k, **kw)
                 done = torch.cuda.Event()
                 done.record(pre)
             scan.wait_event(done)

@@ -254,3 +254,63 @@ def quant_fp8(x: torch.Tensor, out: torch.Tensor | None = None, scale: float = F
 def fp8_to_float(b: torch.Tensor, scale: float = FP8_SCALE) -> torch.Tensor:
     """Reference decode of e4m3 bytes (torch float8_e4m3fn == gfx950's OCP format)."""
     return b.view(torch.float8_e4m3fn).float() / scale
+
+
+FILTER_DIMS = (384, 768, 1024)   # row widths of the masked scan (index_filter.hip)
+
+
+def filter_tiles(mask_words: torch.Tensor, n_valid: int):
+    """Packed row mask (int64 words, bit r % 64 of word r // 64 = row r allowed) -> (tiles int32
+    [max(n_words, 1)], n_live int32 [1]): the ascending 64-row tiles that hold an allowed row
+    below ``n_valid`` and their count, both left on the device (nothing is read back)."""
+    _chk(mask_words, torch.int64, "mask_words", 1)
+    n_words = mask_words.numel()
+    n_valid = int(n_valid)
+    if n_valid < 0 or (n_valid + 63) // 64 > n_words:
+        raise ValueError(f"filter_tiles: {n_words} mask words do not cover {n_valid} rows")
+    dev = mask_words.device
+    tiles = torch.empty(max(n_words, 1), dtype=torch.int32, device=dev)
+    n_live = torch.empty(1, dtype=torch.int32, device=dev)
+    blk_cnt = torch.empty(256, dtype=torch.int32, device=dev)
+    hip().filter_tiles(_ptr(mask_words), n_words, n_valid, _ptr(blk_cnt), _ptr(tiles),
+                       _ptr(n_live), stream_handle(dev))
+    return tiles, n_live
+
+
+def index_scan_filter(rows: torch.Tensor, n_valid: int, mask_words: torch.Tensor,
+                      tiles: torch.Tensor, n_live: torch.Tensor, q_unit: torch.Tensor, kmax: int,
+                      n_rblk: int, cand_s: torch.Tensor, cand_i: torch.Tensor,
+                      thr_init: torch.Tensor | None = None, stride: int = 1, xcd: int = 1) -> None:
+    """The masked list scan: candidates [NQ][n_rblk][lists][kmax] (``topk_geometry``) of the
+    allowed rows below ``n_valid``, for ``topk_merge``.  ``tiles`` / ``n_live`` are
+    ``filter_tiles(mask_words, n_valid)``; ``stride`` walks every stride-th live tile of each
+    workgroup's slice only (a seed pass)."""
+    _chk(rows, torch.bfloat16, "rows", 2)
+    _chk(q_unit, torch.bfloat16, "q_unit", 2)
+    _chk(mask_words, torch.int64, "mask_words", 1)
+    _chk(tiles, torch.int32, "tiles", 1)
+    _chk(n_live, torch.int32, "n_live", 1)
+    _chk(cand_s, torch.float32, "cand_s")
+    _chk(cand_i, torch.int32, "cand_i")
+    D = rows.shape[1]
+    NQ = q_unit.shape[0]
+    n_valid, n_rblk, stride = int(n_valid), int(n_rblk), int(stride)
+    if D not in FILTER_DIMS or q_unit.shape[1] != D:
+        raise ValueError(f"index_scan_filter: rows must be {FILTER_DIMS} wide, queries alike")
+    if kmax not in (16, 32) or stride < 1 or n_rblk < 1:
+        raise ValueError("index_scan_filter: kmax in (16, 32), stride >= 1, n_rblk >= 1")
+    n_tiles = (n_valid + 63) // 64
+    # every tile the list can name lies inside the row slab and has a mask word
+    if n_tiles * 64 > rows.shape[0] or n_tiles > mask_words.numel() or n_tiles > tiles.numel():
+        raise ValueError("index_scan_filter: rows / mask / tile list shorter than n_valid")
+    lists, _ = hip().topk_geometry(D, kmax)
+    need = NQ * n_rblk * lists * kmax
+    if cand_s.numel() < need or cand_i.numel() < need:
+        raise ValueError("index_scan_filter: candidate workspace too small")
+    if thr_init is not None:
+        _chk(thr_init, torch.float32, "thr_init", 1)
+        if thr_init.numel() < NQ:
+            raise ValueError("index_scan_filter: thr_init shorter than the batch")
+    hip().index_scan_filter(_ptr(rows), n_valid, D, _ptr(tiles), _ptr(n_live), _ptr(mask_words),
+                            stride, n_rblk, _ptr(q_unit), NQ, kmax, _ptr(cand_s), _ptr(cand_i),
+                            stream_handle(rows.device), _ptr(thr_init), xcd)

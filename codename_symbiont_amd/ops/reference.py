@@ -118,6 +118,30 @@ def topk_ref(index_rows: torch.Tensor, queries: torch.Tensor, k: int):
     return v, torch.gather(torch.cat(ix, 1), 1, j)
 
 
+def filtered_topk_ref(index_rows: torch.Tensor, queries: torch.Tensor, k: int,
+                      allow_bool: torch.Tensor):
+    """Exact cosine top-k over the rows ``allow_bool`` [n] marks (fp32 math on the same bf16
+    data, in row chunks as ``topk_ref``): disallowed scores go to -inf before the selection.
+    Always [NQ, k]; slots past the allowed rows are (-inf, -1)."""
+    qf = queries.float()
+    n, NQ = index_rows.shape[0], qf.shape[0]
+    allow = torch.as_tensor(allow_bool, dtype=torch.bool, device=index_rows.device)
+    if allow.numel() != n:
+        raise ValueError(f"filtered_topk_ref: {allow.numel()} mask entries for {n} rows")
+    chunk = max(4096, (1 << 26) // max(1, NQ))
+    vs = [torch.full((NQ, k), -math.inf, device=index_rows.device)]
+    ix = [torch.full((NQ, k), -1, dtype=torch.int64, device=index_rows.device)]
+    for s in range(0, n, chunk):
+        sc = qf @ index_rows[s:s + chunk].float().t()
+        sc.masked_fill_(~allow[s:s + chunk][None, :], -math.inf)
+        v, i = torch.topk(sc, min(k, sc.shape[1]), dim=1)
+        vs.append(v)
+        ix.append(i + s)
+    v, j = torch.topk(torch.cat(vs, 1), k, dim=1)
+    i = torch.gather(torch.cat(ix, 1), 1, j)
+    return v, torch.where(torch.isfinite(v), i, torch.full_like(i, -1))
+
+
 def row_scores_ref(index_rows: torch.Tensor, queries: torch.Tensor, r: torch.Tensor):
     """Exact fp32 scores of the rows r [NQ, k] a search returned (no full score matrix)."""
     if r.numel() and int(r.min()) < 0:

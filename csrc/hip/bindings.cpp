@@ -83,6 +83,13 @@ int symb_index_scan_fp8(const void* X, int n_valid, int D, int rows_per_blk, int
 int symb_topk_merge(const float* cand_s, const int* cand_i, int NQ, int n_cand_per_query,
                     int kmax, int k, float* out_s, int* out_i, int64_t id_offset,
                     int64_t* out_id64, hipStream_t st, const int* gate = nullptr);
+// the masked scan (index_filter.hip)
+int symb_filter_tiles(const void* mask, int n_words, int n_valid, int* blk_cnt, int* tiles,
+                      int* n_live, hipStream_t st);
+int symb_index_scan_filter(const void* X, int n_valid, int D, const int* tiles, const int* n_live,
+                           const void* mask, int stride, int n_rblk, const void* Q, int NQ,
+                           int kmax, float* cand_s, int* cand_i, hipStream_t st,
+                           const float* thr_init, int xcd);
 int symb_mq_queries_per_blk(int sets, int rsplit);
 int symb_i8_queries_per_blk(int rsplit);
 int symb_index_scan_i8(const void* X8, const float* sx, int n_valid, int alloc_rows,
@@ -895,6 +902,25 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("Q"), py::arg("NQ"), py::arg("kmax"), py::arg("cand_s"), py::arg("cand_i"),
      py::arg("stream"), py::arg("aux") = -1, py::arg("thr_init") = 0, py::arg("variant") = 0,
      py::arg("xcd") = 1);
+  m.def("filter_tiles", [](uptr mask, int n_words, int n_valid, uptr blk_cnt, uptr tiles,
+                           uptr n_live, uptr st) {
+    check(symb_filter_tiles(P<void>(mask), n_words, n_valid, P<int>(blk_cnt), P<int>(tiles),
+                            P<int>(n_live), S(st)),
+          "filter_tiles");
+  }, py::arg("mask"), py::arg("n_words"), py::arg("n_valid"), py::arg("blk_cnt"),
+     py::arg("tiles"), py::arg("n_live"), py::arg("stream"));
+  m.def("index_scan_filter", [](uptr X, int n_valid, int D, uptr tiles, uptr n_live, uptr mask,
+                                int stride, int n_rblk, uptr Q, int NQ, int kmax, uptr cand_s,
+                                uptr cand_i, uptr st, uptr thr, int xcd) {
+    check(symb_index_scan_filter(P<void>(X), n_valid, D, P<const int>(tiles),
+                                 P<const int>(n_live), P<void>(mask), stride, n_rblk, P<void>(Q),
+                                 NQ, kmax, P<float>(cand_s), P<int>(cand_i), S(st),
+                                 P<const float>(thr), xcd),
+          "index_scan_filter");
+  }, py::arg("X"), py::arg("n_valid"), py::arg("D"), py::arg("tiles"), py::arg("n_live"),
+     py::arg("mask"), py::arg("stride"), py::arg("n_rblk"), py::arg("Q"), py::arg("NQ"),
+     py::arg("kmax"), py::arg("cand_s"), py::arg("cand_i"), py::arg("stream"),
+     py::arg("thr_init") = 0, py::arg("xcd") = 1);
   m.def("topk_merge", [](uptr cand_s, uptr cand_i, int NQ, int n_cand, int kmax, int k,
                          uptr out_s, uptr out_i, int64_t id_offset, uptr out_id64, uptr st,
                          uptr gate) {

@@ -1,4 +1,5 @@
-// Shared pieces of the index scan kernels (bf16: index_topk.hip, fp8: index_fp8.hip).
+// Shared pieces of the index scan kernels (bf16: index_topk.hip, index_filter.hip; fp8:
+// index_fp8.hip).
 #pragma once
 #include "common.h"
 
@@ -66,6 +67,54 @@ __device__ __forceinline__ void topk_insert_par(float (&tv)[KMAX], int (&ti)[KMA
     tv[i] = nv[i];
     ti[i] = ni[i];
   }
+}
+
+constexpr int TOPK_WAVES = 8;
+
+// ---- hand-counted LDS fragment pipeline -------------------------------------------------------
+// hipcc will not count ds_reads around the DMA ring (it drains lgkmcnt(0) before every few MFMAs),
+// so the A fragments are read by inline asm and each MFMA waits with a counted lgkmcnt(N) whose
+// asm names the fragment as "+v" (the MFMA depends on it and cannot be hoisted above the wait).
+template <int OFF>
+__device__ __forceinline__ void ds_read16(bf16x8& dst, uint32_t addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
+}
+template <int N>
+__device__ __forceinline__ void lgkm_wait(bf16x8& v) {
+  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "i"(N));
+}
+
+// Fragment ks lives at  base + voff[ks % M] + (ks / M) * 256  (the XOR swizzle only touches the
+// low 4 bits of the 16-byte chunk index, so the per-lane part repeats every M k-steps).
+// DMA (functor, may be a no-op): DMA(i) issues LDS-DMA piece i of the next tile; pieces are
+// spread one per DMA_EVERY MFMAs so the waves' DMA issue interleaves with their matrix work.
+template <int KS, int NKS, int PF, int M, bool M32, int DMA_EVERY = 0, int DMA_PIECES = 0>
+struct FragChain {
+  static constexpr int R = PF + 1;  // ring slots: a slot is refilled one MFMA after its last use
+  template <class Acc, class Dma = NoDma>
+  __device__ __forceinline__ static void run(Acc& acc, bf16x8 (&a)[R], const bf16x8 (&qf)[NKS],
+                                             const uint32_t (&voff)[M], uint32_t base,
+                                             const Dma& dma = Dma()) {
+    if constexpr (DMA_EVERY > 0 && KS % DMA_EVERY == 0 && KS / DMA_EVERY < DMA_PIECES)
+      dma(KS / DMA_EVERY);
+    constexpr int outstanding = (NKS - KS < PF) ? (NKS - KS) : PF;
+    lgkm_wait<outstanding - 1>(a[KS % R]);
+    if constexpr (M32)
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[KS % R], qf[KS], acc, 0, 0, 0);
+    else
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[KS % R], qf[KS], acc, 0, 0, 0);
+    if constexpr (KS + PF < NKS)
+      ds_read16<((KS + PF) / M) * 256>(a[(KS + PF) % R], base + voff[(KS + PF) % M]);
+    if constexpr (KS + 1 < NKS)
+      FragChain<KS + 1, NKS, PF, M, M32, DMA_EVERY, DMA_PIECES>::run(acc, a, qf, voff, base, dma);
+  }
+};
+
+template <int J, int PF, int M, int R>
+__device__ __forceinline__ void frag_prologue(bf16x8 (&a)[R], const uint32_t (&voff)[M],
+                                              uint32_t base) {
+  ds_read16<(J / M) * 256>(a[J % R], base + voff[J % M]);
+  if constexpr (J + 1 < PF) frag_prologue<J + 1, PF, M, R>(a, voff, base);
 }
 
 }  // namespace symb

@@ -1,0 +1,319 @@
+"""The masked list scan (csrc/hip/index_filter.hip) and the filtered search built on it, against
+ops/reference.filtered_topk_ref and against the unfiltered list scan over the gathered rows.
+
+Shapes are the smallest at which the kernel can go wrong: 64 * 37 + 19 rows (a partial last tile,
+few workgroups) and 20 011 rows (several workgroups, slices of more than the ring's depth).
+Tolerances are the suite's standing ones for a scan against the fp32 reference
+(test_kernels_gpu.py::test_index_scan_topk_exact): scores and true scores atol 2e-3, recall above
+0.995; the conditions on WHICH rows may come back carry no tolerance."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from codename_symbiont_amd.ops import reference as R
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+N_SMALL = 64 * 37 + 19
+N_BIG = 20_011
+CASES = [(D, k, nq) for D in (384, 768, 1024) for k, nq in ((10, 1), (10, 300), (32, 130))]
+
+_shards = {}
+
+
+def _shard(D, n):
+    """One random shard per (width, rows) for the whole module (never written after this)."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    key = (D, n)
+    if key not in _shards:
+        sh = HbmIndexShard(D, n + 100)
+        sh.fill_random(n, seed=5 + D + n)
+        _shards[key] = sh
+    return _shards[key]
+
+
+def _queries(nq, D, seed=11):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return torch.nn.functional.normalize(torch.randn(nq, D, generator=g), dim=-1).bfloat16().to(DEV)
+
+
+def _tiles_mask(n, tiles):
+    a = torch.zeros(n, dtype=torch.bool)
+    for t in tiles:
+        a[t * 64:(t + 1) * 64] = True
+    return a
+
+
+def _masks(n, k):
+    """name -> (bool [n] on the host, random?)."""
+    nt = (n + 63) // 64
+    rng = np.random.default_rng(n + k)
+    rows = lambda idx: torch.zeros(n, dtype=torch.bool).index_fill_(0, torch.as_tensor(idx), True)
+    per_tile = [t * 64 + (t * 7) % 64 for t in range(nt)]
+    m = {
+        "ones": (torch.ones(n, dtype=torch.bool), False),
+        "zero": (torch.zeros(n, dtype=torch.bool), False),
+        "one row": (rows([777 % n]), False),
+        "k-1 rows": (rows(rng.choice(n, k - 1, replace=False)), False),
+        "one bit per tile": (rows([r for r in per_tile if r < n]), False),
+        "alternate tiles dead": (_tiles_mask(n, range(0, nt, 2)), False),
+        "1 live tile": (_tiles_mask(n, [5]), False),
+        "2 live tiles": (_tiles_mask(n, [5, nt - 2]), False),
+        "3 live tiles": (_tiles_mask(n, [0, 9, 20]), False),
+        "7 live tiles": (_tiles_mask(n, [1, 2, 3, 11, 17, 30, nt - 2]), False),
+        "partial last tile only": (rows(list(range((nt - 1) * 64, n))), False),
+        "uniform 50%": (torch.from_numpy(rng.random(n) < 0.5), True),
+        "uniform 1%": (torch.from_numpy(rng.random(n) < 0.01), True),
+    }
+    return m
+
+
+def _close(out, ref, atol, what):
+    err = (out.float() - ref.float()).abs()
+    bad = int((err > atol).sum())
+    assert bad == 0, f"{what}: {bad} elems off, max err {float(err.max()):.4g}"
+
+
+def _check(sh, q, k, allow, what, random_mask=False, arg=None):
+    """One filtered search against the reference; returns (scores, rows)."""
+    n = sh.visible
+    s, r = sh.search(q, k, allow=allow.to(DEV) if arg is None else arg)
+    allow_d = allow.to(DEV)
+    rows = sh.unit_rows()[:n]
+    ref_s, ref_i = R.filtered_topk_ref(rows, q, k, allow_d)
+    torch.cuda.synchronize()
+    assert s.shape == (q.shape[0], k) and r.shape == (q.shape[0], k), what
+    assert s.dtype == torch.float32 and r.dtype == torch.int32, what
+    fin = torch.isfinite(ref_s)
+    n_allowed = int(allow.sum())
+    assert int(fin[0].sum()) == min(k, n_allowed), what
+    # the (-inf, -1) tail is exactly where the reference has it
+    assert torch.equal(torch.isfinite(s), fin), what
+    assert bool((s[~fin] == -math.inf).all()) and bool((r[~fin] == -1).all()), what
+    rr = r.long()
+    got = rr[fin]
+    # hard conditions: allowed rows only, none at or past `visible`, none twice
+    assert bool((got >= 0).all()) and bool((got < n).all()), what
+    assert bool(allow_d[got].all()), f"{what}: a disallowed row came back"
+    srt = torch.sort(torch.where(fin, rr, torch.arange(-k, 0, device=DEV).expand_as(rr)), 1).values
+    assert bool((srt[:, 1:] != srt[:, :-1]).all()), f"{what}: a row came back twice"
+    _close(s[fin], ref_s[fin], 2e-3, f"{what}: scores")
+    true = R.row_scores_ref(rows, q, rr.clamp_min(0))
+    _close(s[fin], true[fin], 2e-3, f"{what}: returned rows' true scores")
+    if n_allowed <= k:
+        want = torch.nonzero(allow_d).flatten()
+        have = torch.sort(rr[:, :n_allowed], 1).values
+        assert torch.equal(have, want.expand_as(have)), f"{what}: not the allowed set"
+    if random_mask:
+        hit = ((rr[:, :, None] == ref_i[:, None, :]) & fin[:, :, None]).any(-1).sum()
+        assert float(hit) / float(fin.sum()) > 0.995, what
+    return s, r
+
+
+@pytest.mark.parametrize("D,k,nq", CASES)
+def test_filtered_search_masks(D, k, nq):
+    q = _queries(nq, D)
+    for n in (N_SMALL, N_BIG):
+        sh = _shard(D, n)
+        for name, (allow, rnd) in _masks(n, k).items():
+            _check(sh, q, k, allow, f"D={D} n={n} k={k} nq={nq} {name}", rnd)
+
+
+def test_mask_input_forms_and_bits_past_visible():
+    """Row list, host array and packed bytes with every bit past `visible` set give the bool
+    mask's result; so does the raw kernel pair on dirty words, with copies of the queries sitting
+    in the slab's rows past `visible` (a scan that ignored n_valid would return them at 1.0)."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+    from codename_symbiont_amd.ops import kernels as K
+    from codename_symbiont_amd.ops._ext import hip, stream_handle
+
+    D, n, k, nq = 384, N_SMALL, 10, 19
+    sh = HbmIndexShard(D, n + 100)
+    sh.fill_random(n, seed=3)
+    q = _queries(nq, D)
+    sh.rows[n:n + nq].copy_(q)                      # unpublished rows of the last tile and beyond
+    allow = torch.from_numpy(np.random.default_rng(4).random(n) < 0.2)
+    s0, r0 = _check(sh, q, k, allow, "bool")
+    dirty = np.full((n + 63) // 64 * 8 + 24, 0xFF, dtype=np.uint8)
+    packed = np.packbits(allow.numpy(), bitorder="little")
+    dirty[:packed.size] = packed
+    dirty[n // 8] |= (0xFF << (n % 8)) & 0xFF
+    for what, arg in (("rows", torch.nonzero(allow).flatten().tolist()), ("numpy", allow.numpy()),
+                      ("packed", dirty), ("bytes", dirty.tobytes()),
+                      ("device packed", torch.from_numpy(dirty).to(DEV))):
+        s, r = _check(sh, q, k, allow, what, arg=arg)
+        assert torch.equal(s, s0) and torch.equal(r, r0), what
+    # the kernels themselves on words whose bits past n are all set
+    nw = (n + 63) // 64
+    words = torch.from_numpy(dirty[:nw * 8].copy()).to(DEV).view(torch.int64)
+    tiles, n_live = K.filter_tiles(words, n)
+    lists, _ = hip().topk_geometry(D, 16)
+    n_rblk = 5
+    cs = torch.empty(nq, n_rblk * lists * 16, device=DEV)
+    ci = torch.empty(nq, n_rblk * lists * 16, dtype=torch.int32, device=DEV)
+    K.index_scan_filter(sh.rows, n, words, tiles, n_live, q, 16, n_rblk, cs, ci)
+    out_s = torch.empty(nq, k, device=DEV)
+    out_i = torch.empty(nq, k, dtype=torch.int32, device=DEV)
+    hip().topk_merge(cs.data_ptr(), ci.data_ptr(), nq, cs.shape[1], 16, k, out_s.data_ptr(),
+                     out_i.data_ptr(), 0, 0, stream_handle(sh.device), 0)
+    torch.cuda.synchronize()
+    assert int(n_live) == len({int(t) // 64 for t in torch.nonzero(allow).flatten()})
+    assert torch.equal(out_s, s0) and torch.equal(out_i, r0)
+
+
+def test_filter_tiles_is_the_ascending_live_list():
+    """Against torch, over one workgroup, several workgroups and several rounds per workgroup
+    (70 000 words: 256 workgroups x 274 words), with n_valid cutting the last word."""
+    from codename_symbiont_amd.ops import kernels as K
+
+    rng = np.random.default_rng(8)
+    for n_words, share in ((1, 1.0), (37, 0.5), (300, 0.02), (5000, 0.5), (70_000, 0.1), (70_000, 0.0)):
+        n_valid = n_words * 64 - 45
+        w = rng.integers(-2 ** 63, 2 ** 63 - 1, n_words, dtype=np.int64)
+        w[rng.random(n_words) >= share] = 0
+        w[-1] = np.int64(-1) << 30            # only bits at or past n_valid's cut: not live
+        words = torch.from_numpy(w).to(DEV)
+        tiles, n_live = K.filter_tiles(words, n_valid)
+        torch.cuda.synchronize()
+        want = np.nonzero(w[:-1])[0]
+        assert int(n_live) == want.size, (n_words, share)
+        assert np.array_equal(tiles[:want.size].cpu().numpy(), want), (n_words, share)
+    with pytest.raises(ValueError):
+        K.filter_tiles(torch.zeros(3, dtype=torch.int64, device=DEV), 64 * 3 + 1)
+
+
+def test_planted_copies_allowed_found_disallowed_never():
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    D, n, k, nq = 384, N_BIG, 10, 40
+    sh = HbmIndexShard(D, n + 100)
+    sh.fill_random(n, seed=21)
+    q = _queries(nq, D, seed=22)
+    bad = torch.arange(nq) + 100                       # disallowed copies, in live tiles 1 and 2
+    good = (torch.arange(nq) + 50) * 64 + 5            # allowed copies, each alone in its tile
+    sh.rows[bad.to(DEV)] = q
+    sh.rows[good.to(DEV)] = q
+    allow = torch.zeros(n, dtype=torch.bool)
+    allow[:40 * 64] = torch.from_numpy(np.random.default_rng(5).random(40 * 64) < 0.1)
+    allow[bad] = False
+    allow[good] = True
+    s_all, r_all = sh.search(q, k)
+    s, r = _check(sh, q, k, allow, "planted")
+    assert bool((s_all[:, 0] > 0.99).all())
+    assert bool(((r_all[:, :2].long() == bad.to(DEV)[:, None]).any(1)).all())
+    assert torch.equal(r[:, 0].long(), good.to(DEV)) and bool((s[:, 0] > 0.99).all())
+    assert not bool((r.long()[:, :, None] == bad.to(DEV)[None, None, :]).any())
+
+
+@pytest.mark.parametrize("D,k,nq", [(384, 10, 300), (768, 10, 130), (1024, 32, 64)])
+def test_filtered_equals_list_scan_over_gathered_rows(D, k, nq):
+    """Per row the MFMA chain is the unfiltered kernel's, unchanged in order, so the filtered
+    scores equal the list scan's over the index_select-ed allowed rows (atol 1e-6, the suite's
+    figure for same-kernel repeats), ids mapped back."""
+    sh = _shard(D, N_BIG)
+    q = _queries(nq, D, seed=31)
+    rng = np.random.default_rng(6)
+    docs = torch.zeros(N_BIG, dtype=torch.bool)
+    for s0 in rng.choice(N_BIG - 200, 12, replace=False):
+        docs[s0:s0 + 200] = True
+    kmax = 16 if k <= 16 else 32
+    for what, allow in (("uniform 50%", torch.from_numpy(rng.random(N_BIG) < 0.5)), ("documents", docs)):
+        idx = torch.nonzero(allow.to(DEV)).flatten()
+        m = idx.numel()
+        sub = torch.zeros((m + 63) // 64 * 64, D, dtype=torch.bfloat16, device=DEV)
+        torch.index_select(sh.rows, 0, idx, out=sub[:m])
+        gs, gi = sh._scan(m, q, kmax, k, None, None, rows=sub)
+        gi = idx[gi.long()]
+        for seed in (False, True):
+            sh.filter_seed = seed
+            try:
+                s, r = sh.search(q, k, allow=allow.to(DEV))
+            finally:
+                sh.filter_seed = type(sh).FILTER_SEED_DEFAULT
+            torch.cuda.synchronize()
+            _close(s, gs, 1e-6, f"{what} seed={seed}")
+            rr = r.long()
+            tie = torch.zeros_like(rr, dtype=torch.bool)
+            tie[:, 1:] |= s[:, 1:] == s[:, :-1]
+            tie[:, :-1] |= s[:, :-1] == s[:, 1:]
+            assert bool(((rr == gi) | tie).all()), f"{what} seed={seed}: rows differ"
+
+
+def test_seed_pass_on_and_off_identical():
+    D, k, nq = 384, 10, 300
+    sh = _shard(D, N_BIG)
+    q = _queries(nq, D, seed=41)
+    masks = _masks(N_BIG, k)
+    try:
+        for name in ("ones", "alternate tiles dead", "uniform 1%", "3 live tiles"):
+            allow = masks[name][0].to(DEV)
+            mask = sh.make_mask(allow)
+            sh.filter_seed = True
+            s1, r1 = sh.search(q, k, allow=mask)
+            sh.filter_seed = False
+            s0, r0 = sh.search(q, k, allow=mask)
+            torch.cuda.synchronize()
+            assert torch.equal(s0, s1) and torch.equal(r0, r1), name
+    finally:
+        sh.filter_seed = type(sh).FILTER_SEED_DEFAULT
+
+
+def test_row_mask_reused_across_an_append():
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    D, n, k, nq = 384, N_SMALL, 10, 30
+    sh = HbmIndexShard(D, n + 100)
+    sh.fill_random(n, seed=7)
+    q = _queries(nq, D, seed=8)
+    mask = sh.make_mask(torch.ones(n, dtype=torch.bool, device=DEV))
+    s0, r0 = sh.search(q, k, allow=mask)
+    sh.append_unit(q)                                  # the queries themselves: unmasked top-1
+    s1, r1 = sh.search(q, k, allow=mask)
+    s_all, r_all = sh.search(q, k)
+    torch.cuda.synchronize()
+    assert torch.equal(r_all[:, 0].long(), torch.arange(n, n + nq, device=DEV))
+    assert int(r1.max()) < n
+    assert torch.equal(s0, s1) and torch.equal(r0, r1)
+    # a mask made now sees them
+    s2, r2 = sh.search(q, k, allow=torch.ones(n + nq, dtype=torch.bool, device=DEV))
+    assert torch.equal(r2[:, 0].long(), torch.arange(n, n + nq, device=DEV))
+
+
+@pytest.mark.parametrize("pipeline", ["0", "1"])
+def test_vector_store_filter_plain_and_pipelined(pipeline, monkeypatch):
+    from codename_symbiont_amd.index.filter import Filter
+    from codename_symbiont_amd.index.shard import Payload
+    from codename_symbiont_amd.index.store import VectorStore
+
+    monkeypatch.setenv("SYMB_SEARCH_PIPELINE", pipeline)
+    D, k = 384, 10
+    st = VectorStore(D, 4096, device="cuda")
+    assert (st._streams is not None) == (pipeline == "1")
+    sizes = {"doc-a": 5, "doc-b": 40, "doc-c": 300}
+    rng = np.random.default_rng(12)
+    ids, pls = [], []
+    for doc, m in sizes.items():
+        for j in range(m):
+            ids.append(f"{doc}/{j}")
+            pls.append(Payload(doc, f"http://{doc}.example", f"s{j}", j, "m", 0))
+    order = rng.permutation(len(ids))                  # documents interleaved over the rows
+    ids, pls = [ids[i] for i in order], [pls[i] for i in order]
+    st.upsert(ids, rng.standard_normal((len(ids), D)).astype(np.float32), pls)
+    q = rng.standard_normal((9, D)).astype(np.float32)
+    for doc, m in sizes.items():
+        s, r = st.search(q, k, filter=Filter(must={"original_document_id": doc}))
+        assert s.shape == (9, k) and r.shape == (9, k)
+        for i in range(9):
+            fin = np.isfinite(s[i])
+            assert int(fin.sum()) == min(k, m) and (r[i][~fin] == -1).all()
+            hits = [st.lookup(int(g)) for g in r[i][fin]]
+            assert all(p.original_document_id == doc for _, p in hits)
+            assert all(pid.startswith(doc + "/") for pid, _ in hits)
+            assert len({pid for pid, _ in hits}) == min(k, m)
+    s, r = st.search(q, k, filter=Filter(must_not={"original_document_id": ["doc-b", "doc-c"]}))
+    assert all(st.lookup(int(g))[1].original_document_id == "doc-a" for g in r[np.isfinite(s)])
+    assert int(np.isfinite(s).sum()) == 9 * 5
