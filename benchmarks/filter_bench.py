@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Filtered search (exact top-k under a row mask, csrc/hip/index_filter.hip) against what a caller
-could do before it, on one bf16 shard of random unit rows with held-out random queries.
+"""Filtered search (exact top-k under a row mask, csrc/hip/index_filter.hip; index_filter_fp8.hip
+with --dtype fp8) against what a caller could do before it, on one shard of random unit rows with
+held-out random queries.
 
 Per mask, in alternated rounds on the same shard (one JSON line per mask and variant):
 
@@ -10,6 +11,15 @@ Per mask, in alternated rounds on the same shard (one JSON line per mask and var
                    the copy, ids mapped back (skipped where the copy does not fit)
   search           the unfiltered shard.search(q, k)            (yardstick, mask-independent)
   plain_scan       the unfiltered, unseeded list scan (_scan)  (yardstick, mask-independent)
+  matmul_mask      (--fallback) the chunked matmul under the mask, the route of every shard the
+                   masked scan does not serve and of fp8 shards before it did: one iteration
+
+--dtype fp8: the shard holds e4m3 rows, gather_scan is the fp8 list scan over the index_select-ed
+bytes, and every record carries "dtype": "fp8", rows_equal_gather (the masked scan's rows against
+gather_scan's: equal outside runs of equal scores, and a last slot that differs without an equal
+neighbour proved a tie by searching its two rows alone, rows_equal_outside_ties) and
+last_slot_ties_proved (how many such slots there were).  Scores are compared in cosine units
+(raw / FP8_SCALE**2).
 
 Masks: all ones; uniform random bits; "documents" = runs of 200 consecutive rows.  The RowMask
 (packed bits + live-tile list) and the gather's row list are built once per mask, outside the
@@ -17,6 +27,7 @@ timed loops; ``mask_ms`` is that one-off cost of the RowMask.
 
     python benchmarks/filter_bench.py [--rows 100000000] [--dim 384] [--nq 256] [--k 10]
         [--masks ones,u50,u10,u1,d10,d1,d0.1] [--rounds 3] [--iters 5] [--out FILE]
+        [--dtype bf16|fp8] [--fallback]
 """
 from __future__ import annotations
 
@@ -52,6 +63,35 @@ def build_allow(name: str, n: int, dev, seed: int) -> torch.Tensor:
     raise ValueError(f"unknown mask {name!r}")
 
 
+def rows_equal_outside_ties(shard, q, s, r, ref_r):
+    """Rows r against ref_r [NQ, k] for scores s both searches agree on -> (equal?, proved).
+    Slots whose score equals a neighbour's are exempt.  A run of equal scores can go on past k,
+    where no neighbour shows it: a last slot that differs with no equal neighbour counts as equal
+    only if neither row is among the other side's rows and the two rows, searched alone under a
+    two-row mask (k = 2), score the same bit for bit, which is the slot's score; ``proved`` counts
+    those slots."""
+    rr, gg = r.long(), ref_r.long()
+    fin = torch.isfinite(s)
+    tie = torch.zeros_like(fin)
+    tie[:, 1:] |= s[:, 1:] == s[:, :-1]
+    tie[:, :-1] |= s[:, :-1] == s[:, 1:]
+    diff = (rr != gg) & ~tie & fin
+    if bool(diff[:, :-1].any()):
+        return False, 0
+    proved = 0
+    for i in torch.nonzero(diff[:, -1]).flatten().tolist():
+        a, b = int(rr[i, -1]), int(gg[i, -1])
+        if a < 0 or b < 0 or b in rr[i].tolist() or a in gg[i].tolist():
+            return False, proved
+        s2, r2 = shard.search(q[i:i + 1], 2, allow=[a, b])
+        if sorted(r2[0].tolist()) != sorted((a, b)):
+            return False, proved
+        if not float(s2[0, 0]) == float(s2[0, 1]) == float(s[i, -1]):
+            return False, proved
+        proved += 1
+    return True, proved
+
+
 def timed(fn, iters: int) -> float:
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -71,19 +111,29 @@ def main() -> None:
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--dtype", choices=("bf16", "fp8"), default="bf16")
+    ap.add_argument("--fallback", action="store_true",
+                    help="also time the chunked matmul under the mask (one iteration)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("filter_bench needs the GPU: nothing here is measured without one")
-    from codename_symbiont_amd.index.shard import TILE_ROWS, HbmIndexShard
+    from codename_symbiont_amd.index.shard import FP8_SCALE, TILE_ROWS, HbmIndexShard
 
     dev = torch.device("cuda")
     n, k = a.rows, a.k
     kmax = 16 if k <= 16 else 32
-    shard = HbmIndexShard(a.dim, n, device=dev)
+    fp8 = a.dtype == "fp8"
+    shard = HbmIndexShard(a.dim, n, device=dev, dtype=a.dtype)
     shard.fill_random(n, seed=1)
     g = torch.Generator(device=dev).manual_seed(77)      # held out: not rows of the shard
     q = torch.nn.functional.normalize(torch.randn(a.nq, a.dim, device=dev, generator=g),
                                       dim=-1).bfloat16()
+    q8 = None
+    if fp8:
+        from codename_symbiont_amd.ops.kernels import quant_fp8
+
+        q8 = quant_fp8(q, scale=FP8_SCALE)
+    row_bytes = a.dim * (1 if fp8 else 2)
     out = open(a.out, "a") if a.out else None
 
     def emit(rec):
@@ -95,6 +145,8 @@ def main() -> None:
 
     base = {"bench": "filter_bench", "rows": n, "dim": a.dim, "nq": a.nq, "k": k,
             "rounds": a.rounds, "iters": a.iters}
+    if fp8:
+        base["dtype"] = "fp8"
     for mi, name in enumerate(a.masks.split(",")):
         allow = build_allow(name, n, dev, 100 + mi)
         torch.cuda.synchronize()
@@ -111,8 +163,9 @@ def main() -> None:
         m = idx.numel()
         m_pad = (m + TILE_ROWS - 1) // TILE_ROWS * TILE_ROWS
         free, _ = torch.cuda.mem_get_info(dev)
-        gather_ok = m > 0 and m_pad * a.dim * 2 < free - (8 << 30)
-        sub = torch.zeros(m_pad, a.dim, dtype=torch.bfloat16, device=dev) if gather_ok else None
+        gather_ok = m > 0 and m_pad * row_bytes < free - (8 << 30)
+        sub = (torch.zeros(m_pad, a.dim, dtype=shard.rows.dtype, device=dev) if gather_ok
+               else None)
 
         def filtered(seed):
             shard.filter_seed = seed
@@ -120,13 +173,17 @@ def main() -> None:
 
         def gather():
             torch.index_select(shard.rows, 0, idx, out=sub[:m])
-            s, r = shard._scan(m, q, kmax, k, None, None, rows=sub)
+            if fp8:
+                s, r = shard._scan(m, q8, kmax, k, None, None, rows=sub, dtype="fp8")
+                s = s * (1.0 / (FP8_SCALE * FP8_SCALE))
+            else:
+                s, r = shard._scan(m, q, kmax, k, None, None, rows=sub)
             return s, idx[r.long().clamp_min(0)]
 
         variants = {"filtered_seed": lambda: filtered(True),
                     "filtered_noseed": lambda: filtered(False),
                     "search": lambda: shard.search(q, k),
-                    "plain_scan": lambda: shard._scan(n, q, kmax, k, None, None)}
+                    "plain_scan": lambda: shard._scan(n, q8 if fp8 else q, kmax, k, None, None)}
         if gather_ok:
             variants["gather_scan"] = gather
         # results first (also the warm-up of every shape): seed on == seed off == gather
@@ -137,6 +194,14 @@ def main() -> None:
         same_gather = None
         if gather_ok:
             same_gather = bool(torch.equal(res["filtered_seed"][0], res["gather_scan"][0]))
+        extra = {}
+        if fp8 and gather_ok:
+            (fs, fr), (gs, gr) = res["filtered_seed"], res["gather_scan"]
+            fin = torch.isfinite(gs)
+            err = torch.where(fin, (fs - gs).abs(), torch.zeros_like(gs))
+            same_rows, proved = rows_equal_outside_ties(shard, q, gs, fr, gr)
+            extra = {"max_abs_vs_gather": float(err.max()), "rows_equal_gather": same_rows,
+                     "last_slot_ties_proved": proved}
         del res
         times = {v: [] for v in variants}
         for _ in range(a.rounds):            # alternated: every variant once per round
@@ -145,7 +210,11 @@ def main() -> None:
         for v, ts in times.items():
             emit(dict(info, variant=v, ms=round(statistics.median(ts), 3),
                       ms_min=round(min(ts), 3), ms_max=round(max(ts), 3),
-                      seed_on_equals_off=same_seed, scores_equal_gather=same_gather))
+                      seed_on_equals_off=same_seed, scores_equal_gather=same_gather, **extra))
+        if a.fallback:
+            ms = timed(lambda: shard._search_matmul(q, k, mask=mask), 1)
+            emit(dict(info, variant="matmul_mask", ms=round(ms, 3), ms_min=round(ms, 3),
+                      ms_max=round(ms, 3), iters=1, rounds=1))
         del sub, idx, mask
         torch.cuda.empty_cache()
 

@@ -196,6 +196,7 @@ I8_RING_DIMS = (768,)
 
 
 FILTER_DIMS = (384, 768, 1024)          # ... the masked list scan (index_filter.hip)
+FILTER_FP8_DIMS = (256, 384, 512, 768, 1024)   # ... its e4m3 form (index_filter_fp8.hip)
 
 
 def _pack_bits(allow: torch.Tensor, n_words: int) -> torch.Tensor:
@@ -1060,18 +1061,25 @@ class HbmIndexShard:
             raise TypeError(f"make_mask: bool mask, int rows or packed uint8 bits, got {a.dtype}")
         bits = _pack_bits(ok, max(1, (v + TILE_ROWS - 1) // TILE_ROWS))
         tiles = n_live = None
-        if dev.type == "cuda" and self.dtype == "bf16" and self.dim in FILTER_DIMS:
+        if dev.type == "cuda" and self._filter_scan_serves():
             from ..ops.kernels import filter_tiles
 
             tiles, n_live = filter_tiles(bits.view(torch.int64), v)
         return RowMask(bits, v, tiles, n_live)
 
+    def _filter_scan_serves(self) -> bool:
+        """A masked list scan exists for this shard's row format and width."""
+        return ((self.dtype == "bf16" and self.dim in FILTER_DIMS)
+                or (self.dtype == "fp8" and self.dim in FILTER_FP8_DIMS))
+
     def _search_masked(self, q_unit, k: int, n_cus, allow):
-        """``search`` under a row mask, exact over the allowed bf16 rows.  A GPU bf16 shard of a
-        width in FILTER_DIMS at k <= 32 takes the masked list scan; everything else (CPU and fp8
-        shards, k > 32, other widths) the chunked matmul with the score block masked.  The cheap
-        routes of the unmasked search do not apply: their thresholds come from a sample of ALL
-        rows, which is no lower bound on the k-th allowed score."""
+        """``search`` under a row mask, exact over the allowed rows.  A GPU shard at k <= 32 takes
+        the masked list scan of its row format (bf16 at a width in FILTER_DIMS, fp8 at one in
+        FILTER_FP8_DIMS); everything else (CPU shards, k > 32, other widths) the chunked matmul
+        with the score block masked.  On an fp8 shard the list scan scores e4m3(q) . e4m3(x), as
+        the unmasked GPU search does; the matmul scores float(q) . decode(x).  The cheap routes of
+        the unmasked search do not apply: their thresholds come from a sample of ALL rows, which
+        is no lower bound on the k-th allowed score."""
         NQ = q_unit.shape[0]
         k = int(k)
         if NQ == 0 or k <= 0:
@@ -1080,18 +1088,19 @@ class HbmIndexShard:
         mask = self.make_mask(allow)
         if mask.bits.device != self.device:
             raise ValueError(f"RowMask on {mask.bits.device}, shard on {self.device}")
-        if (self.device.type == "cuda" and self.dtype == "bf16" and self.dim in FILTER_DIMS
-                and k <= 32 and mask.tiles is not None):
+        if (self.device.type == "cuda" and self._filter_scan_serves() and k <= 32
+                and mask.tiles is not None):
             return self._search_filtered(q_unit.to(torch.bfloat16).contiguous(), k, mask, n_cus)
         return self._search_matmul(q_unit, k, mask=mask)
 
     def _search_filtered(self, q_unit, k: int, mask: RowMask, n_cus):
-        """The masked list scan (index_filter.hip) + merge.  The grid and the candidate
-        workspace are sized as if every tile were live; the kernel reads the live count on the
-        device.  ``filter_seed``: a first pass over every FILTER_SEED_STRIDE-th live tile of each
-        workgroup's slice sees allowed rows only, so its k-th best is a lower bound on the final
-        k-th allowed score (-inf where it found fewer than k rows); the full pass starts from
-        it.  Exact either way."""
+        """The masked list scan (index_filter.hip; index_filter_fp8.hip on an fp8 shard, whose
+        queries are quantised to e4m3 here and whose raw scores, S^2 * cosine, are rescaled once
+        at the end) + merge.  The grid and the candidate workspace are sized as if every tile
+        were live; the kernel reads the live count on the device.  ``filter_seed``: a first pass
+        over every FILTER_SEED_STRIDE-th live tile of each workgroup's slice sees allowed rows
+        only, so its k-th best is a lower bound on the final k-th allowed score (-inf where it
+        found fewer than k rows); the full pass starts from it.  Exact either way."""
         from ..ops import kernels as K
         from ..ops._ext import hip, stream_handle
 
@@ -1103,7 +1112,12 @@ class HbmIndexShard:
         out_i = torch.empty(NQ, k, dtype=torch.int32, device=dev)
         if n <= 0:
             return out_s.fill_(-math.inf), out_i.fill_(-1)
-        lists, qpb = h.topk_geometry(self.dim, kmax)
+        fp8 = self.dtype == "fp8"
+        if fp8:
+            q_unit = K.quant_fp8(q_unit, scale=FP8_SCALE)
+            scan, (lists, qpb) = K.index_scan_filter_fp8, (2, 256)
+        else:
+            scan, (lists, qpb) = K.index_scan_filter, h.topk_geometry(self.dim, kmax)
         n_qblk = math.ceil(NQ / qpb)
         if n_cus is None:
             n_cus = self._n_cus()
@@ -1115,8 +1129,8 @@ class HbmIndexShard:
         st = stream_handle(dev)
 
         def one_pass(thr, stride):
-            K.index_scan_filter(self.rows, n, mask.words, mask.tiles, mask.n_live, q_unit, kmax,
-                                n_rblk, cs, ci, thr, stride, self.scan_xcd)
+            scan(self.rows, n, mask.words, mask.tiles, mask.n_live, q_unit, kmax, n_rblk, cs, ci,
+                 thr, stride, self.scan_xcd)
             h.topk_merge(cs.data_ptr(), ci.data_ptr(), NQ, ncand, kmax, k, out_s.data_ptr(),
                          out_i.data_ptr(), 0, 0, st, 0)
 
@@ -1126,6 +1140,8 @@ class HbmIndexShard:
             kth = out_s[:, k - 1].contiguous()
             thr = torch.nextafter(kth, torch.full_like(kth, -math.inf))
         one_pass(thr, 1)
+        if fp8:
+            out_s.mul_(1.0 / (FP8_SCALE * FP8_SCALE))   # (-inf stays -inf)
         return out_s, out_i
 
     def _search_scan(self, q_unit, k: int, rows, dtype: str, n_cus):

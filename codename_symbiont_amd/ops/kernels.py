@@ -314,3 +314,51 @@ def index_scan_filter(rows: torch.Tensor, n_valid: int, mask_words: torch.Tensor
     hip().index_scan_filter(_ptr(rows), n_valid, D, _ptr(tiles), _ptr(n_live), _ptr(mask_words),
                             stride, n_rblk, _ptr(q_unit), NQ, kmax, _ptr(cand_s), _ptr(cand_i),
                             stream_handle(rows.device), _ptr(thr_init), xcd)
+
+
+FILTER_FP8_DIMS = (256, 384, 512, 768, 1024)   # ... of its e4m3 form (index_filter_fp8.hip)
+
+
+def index_scan_filter_fp8(rows_u8: torch.Tensor, n_valid: int, mask_words: torch.Tensor,
+                          tiles: torch.Tensor, n_live: torch.Tensor, q_e4m3: torch.Tensor,
+                          kmax: int, n_rblk: int, cand_s: torch.Tensor, cand_i: torch.Tensor,
+                          thr_init: torch.Tensor | None = None, stride: int = 1,
+                          xcd: int = 1) -> None:
+    """The masked list scan over e4m3 rows (``quant_fp8`` bytes at FP8_SCALE) for e4m3 queries:
+    candidates [NQ][n_rblk][2][kmax] of the allowed rows below ``n_valid``, for ``topk_merge``.
+    Scores are raw accumulators (FP8_SCALE**2 * cosine) and ``thr_init`` is in the same units.
+    ``tiles`` / ``n_live`` / ``stride`` as in ``index_scan_filter``."""
+    if rows_u8.dtype != torch.uint8 or q_e4m3.dtype != torch.uint8:
+        # (a bf16 slab of the same width would be read as twice as many e4m3 rows)
+        raise ValueError("index_scan_filter_fp8: rows and queries are e4m3 bytes (uint8), got "
+                         f"{rows_u8.dtype} / {q_e4m3.dtype}")
+    _chk(rows_u8, torch.uint8, "rows_u8", 2)
+    _chk(q_e4m3, torch.uint8, "q_e4m3", 2)
+    _chk(mask_words, torch.int64, "mask_words", 1)
+    _chk(tiles, torch.int32, "tiles", 1)
+    _chk(n_live, torch.int32, "n_live", 1)
+    _chk(cand_s, torch.float32, "cand_s")
+    _chk(cand_i, torch.int32, "cand_i")
+    D = rows_u8.shape[1]
+    NQ = q_e4m3.shape[0]
+    n_valid, n_rblk, stride = int(n_valid), int(n_rblk), int(stride)
+    if D not in FILTER_FP8_DIMS or q_e4m3.shape[1] != D:
+        raise ValueError(f"index_scan_filter_fp8: rows must be {FILTER_FP8_DIMS} wide, queries alike")
+    if kmax not in (16, 32) or stride < 1 or n_rblk < 1:
+        raise ValueError("index_scan_filter_fp8: kmax in (16, 32), stride >= 1, n_rblk >= 1")
+    n_tiles = (n_valid + 63) // 64
+    # every tile the list can name lies inside the row slab and has a mask word
+    if (n_valid < 0 or n_tiles * 64 > rows_u8.shape[0] or n_tiles > mask_words.numel()
+            or n_tiles > tiles.numel()):
+        raise ValueError("index_scan_filter_fp8: rows / mask / tile list shorter than n_valid")
+    need = NQ * n_rblk * 2 * kmax
+    if cand_s.numel() < need or cand_i.numel() < need:
+        raise ValueError("index_scan_filter_fp8: candidate workspace too small")
+    if thr_init is not None:
+        _chk(thr_init, torch.float32, "thr_init", 1)
+        if thr_init.numel() < NQ:
+            raise ValueError("index_scan_filter_fp8: thr_init shorter than the batch")
+    hip().index_scan_filter_fp8(_ptr(rows_u8), n_valid, D, _ptr(tiles), _ptr(n_live),
+                                _ptr(mask_words), stride, n_rblk, _ptr(q_e4m3), NQ, kmax,
+                                _ptr(cand_s), _ptr(cand_i), stream_handle(rows_u8.device),
+                                _ptr(thr_init), xcd)

@@ -90,6 +90,12 @@ int symb_index_scan_filter(const void* X, int n_valid, int D, const int* tiles, 
                            const void* mask, int stride, int n_rblk, const void* Q, int NQ,
                            int kmax, float* cand_s, int* cand_i, hipStream_t st,
                            const float* thr_init, int xcd);
+// ... over e4m3 rows (index_filter_fp8.hip)
+int symb_index_scan_filter_fp8(const void* X, int n_valid, int D, const int* tiles,
+                               const int* n_live, const void* mask, int stride, int n_rblk,
+                               const void* Q, int NQ, int kmax, float* cand_s, int* cand_i,
+                               hipStream_t st, const float* thr_init, int xcd);
+int symb_filter_fp8_ring_depth(int D);
 int symb_mq_queries_per_blk(int sets, int rsplit);
 int symb_i8_queries_per_blk(int rsplit);
 int symb_index_scan_i8(const void* X8, const float* sx, int n_valid, int alloc_rows,
@@ -917,6 +923,19 @@ PYBIND11_MODULE(_hip, m) {
                                  NQ, kmax, P<float>(cand_s), P<int>(cand_i), S(st),
                                  P<const float>(thr), xcd),
           "index_scan_filter");
+  }, py::arg("X"), py::arg("n_valid"), py::arg("D"), py::arg("tiles"), py::arg("n_live"),
+     py::arg("mask"), py::arg("stride"), py::arg("n_rblk"), py::arg("Q"), py::arg("NQ"),
+     py::arg("kmax"), py::arg("cand_s"), py::arg("cand_i"), py::arg("stream"),
+     py::arg("thr_init") = 0, py::arg("xcd") = 1);
+  m.def("filter_fp8_ring_depth", &symb_filter_fp8_ring_depth, py::arg("D"));
+  m.def("index_scan_filter_fp8", [](uptr X, int n_valid, int D, uptr tiles, uptr n_live,
+                                    uptr mask, int stride, int n_rblk, uptr Q, int NQ, int kmax,
+                                    uptr cand_s, uptr cand_i, uptr st, uptr thr, int xcd) {
+    check(symb_index_scan_filter_fp8(P<void>(X), n_valid, D, P<const int>(tiles),
+                                     P<const int>(n_live), P<void>(mask), stride, n_rblk,
+                                     P<void>(Q), NQ, kmax, P<float>(cand_s), P<int>(cand_i),
+                                     S(st), P<const float>(thr), xcd),
+          "index_scan_filter_fp8");
   }, py::arg("X"), py::arg("n_valid"), py::arg("D"), py::arg("tiles"), py::arg("n_live"),
      py::arg("mask"), py::arg("stride"), py::arg("n_rblk"), py::arg("Q"), py::arg("NQ"),
      py::arg("kmax"), py::arg("cand_s"), py::arg("cand_i"), py::arg("stream"),

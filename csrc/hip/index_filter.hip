@@ -37,13 +37,7 @@
 
 namespace symb {
 
-// ---- live-tile list ----------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t live_word(uint64_t w, int tile, int n_valid) {
-  const long rem = (long)n_valid - (long)tile * 64;
-  if (rem < 64) w = rem > 0 ? (w & ((1ull << rem) - 1)) : 0ull;
-  return w;
-}
-
+// ---- live-tile list (live_word: scan_common.h) -------------------------------------------------
 constexpr int FT_THREADS = 256;
 
 // block-wide sum of one int per thread (FT_THREADS threads), returned to every thread
@@ -94,18 +88,7 @@ __global__ __launch_bounds__(FT_THREADS) void filter_tiles_kernel(
   }
 }
 
-// ---- hand-issued scalar loads (see the header note) ---------------------------------------------
-__device__ __forceinline__ void sload_i32(int& dst, const int* p) {
-  asm volatile("s_load_dword %0, %1, 0x0" : "=s"(dst) : "s"(p));
-}
-__device__ __forceinline__ void sload_u64(uint64_t& dst, const uint64_t* p) {
-  asm volatile("s_load_dwordx2 %0, %1, 0x0" : "=s"(dst) : "s"(p));
-}
-// every scalar load (and ds_read) of this wave has landed; the asm names the loaded values so no
-// use of them can be scheduled above the wait
-__device__ __forceinline__ void swait(int& a, int& b, uint64_t& w) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a), "+s"(b), "+s"(w)::"memory");
-}
+// (the hand-issued scalar loads of the header note, sload_i32 / sload_u64 / swait: scan_common.h)
 
 // Template parameters as index_scan_topk_kernel (index_topk.hip).  A list entry is a 64-row tile;
 // a barrier interval covers TR = 64 rows at D = 384 and 32 rows at D = 768 / 1024, where one list

@@ -1,5 +1,5 @@
 // Shared pieces of the index scan kernels (bf16: index_topk.hip, index_filter.hip; fp8:
-// index_fp8.hip).
+// index_fp8.hip, index_filter_fp8.hip).
 #pragma once
 #include "common.h"
 
@@ -32,6 +32,38 @@ __device__ __forceinline__ void static_for(F&& f) {
 struct NoDma {
   __device__ __forceinline__ void operator()(int) const {}
 };
+
+// ---- masked scans (index_filter.hip, index_filter_fp8.hip): mask words, hand-issued scalar loads
+// mask word of 64-row tile `tile` with the bits of rows at or past n_valid cleared
+__device__ __forceinline__ uint64_t live_word(uint64_t w, int tile, int n_valid) {
+  const long rem = (long)n_valid - (long)tile * 64;
+  if (rem < 64) w = rem > 0 ? (w & ((1ull << rem) - 1)) : 0ull;
+  return w;
+}
+
+// Tile indices and mask words are wave-uniform, so they are read by scalar loads, issued by hand
+// and waited for by hand (swait): a compiler-placed scalar load would be waited for with
+// lgkmcnt(0) wherever its value is first used, in the middle of a counted ds_read pipeline.
+__device__ __forceinline__ void sload_i32(int& dst, const int* p) {
+  asm volatile("s_load_dword %0, %1, 0x0" : "=s"(dst) : "s"(p));
+}
+__device__ __forceinline__ void sload_u64(uint64_t& dst, const uint64_t* p) {
+  asm volatile("s_load_dwordx2 %0, %1, 0x0" : "=s"(dst) : "s"(p));
+}
+// every scalar load (and ds_read) of this wave has landed; the asm names the loaded values so no
+// use of them can be scheduled above the wait
+__device__ __forceinline__ void swait(int& a, int& b, uint64_t& w) {
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a), "+s"(b), "+s"(w)::"memory");
+}
+
+// the same wait for N loaded ints (volatile asm statements keep their order, so each value is
+// re-defined below the wait)
+template <int N>
+__device__ __forceinline__ void swait_n(int (&v)[N]) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int i = 0; i < N; ++i) asm volatile("" : "+s"(v[i]));
+}
 
 template <int KMAX>
 __device__ __forceinline__ void topk_insert(float (&tv)[KMAX], int (&ti)[KMAX], float s, int id) {
