@@ -67,13 +67,12 @@ def cmd_scan(a):
         ci = torch.empty(a.nq, ncand, dtype=torch.int32, device="cuda")
         st = stream_handle()
         variants = {}
-        for ns in ((2, 3) if D == 384 else (0,)):
-            for aux in (0, 2):
-                for xcd in ((0, 1) if n_qblk > 1 else (0,)):
-                    def f(ns=ns, aux=aux, xcd=xcd):
-                        h.index_scan(shard.rows.data_ptr(), a.rows, D, rpb, n_rblk, q.data_ptr(),
-                                     a.nq, kmax, cs.data_ptr(), ci.data_ptr(), st, ns, aux, 0, xcd)
-                    variants[f"blk{mult}x_ns{ns}_aux{aux}_xcd{xcd}"] = f
+        for aux in (0, 2):
+            for xcd in ((0, 1) if n_qblk > 1 else (0,)):
+                def f(aux=aux, xcd=xcd):
+                    h.index_scan(shard.rows.data_ptr(), a.rows, D, rpb, n_rblk, q.data_ptr(),
+                                 a.nq, kmax, cs.data_ptr(), ci.data_ptr(), st, aux, 0, xcd)
+                variants[f"blk{mult}x_aux{aux}_xcd{xcd}"] = f
         if mult == 1:
             def srch(seed):
                 shard.seed_threshold = seed
@@ -141,19 +140,6 @@ def cmd_scanmq(a):
             torch.cuda.synchronize()
             ids_equal = min(ids_equal, float((ref[1] == got5[1]).float().mean()))
             variants["pruned_i8_rs2"] = rs2
-    from codename_symbiont_amd.ops._ext import hip
-
-    def srch_nt():   # non-temporal row stream
-        hip().mq_config(2)
-        try:
-            return srch(True)
-        finally:
-            hip().mq_config(0)
-
-    got3 = srch_nt()
-    torch.cuda.synchronize()
-    ids_equal = min(ids_equal, float((ref[1] == got3[1]).float().mean()))
-    variants["mq_nt"] = srch_nt
     if a.nq < 512:   # the two 256-query forms: row-split 4-set ("mq512") and 2-set
         got2 = srch(True, False)
         torch.cuda.synchronize()
@@ -174,131 +160,6 @@ def cmd_scanmq(a):
                       "cand_max": int(cnt.max()), "results": out}))
 
 
-def cmd_scanmqabl(a):
-    """index_scan_mq_kernel ablations (abl 0 full, 1 no DMA, 2 no emission test) and its in-kernel
-    clock (abl 3 stamps), same thresholds and grid as shard.search."""
-    from codename_symbiont_amd.index.shard import HbmIndexShard, TILE_ROWS, _round_up
-    from codename_symbiont_amd.ops._ext import hip, stream_handle
-
-    D, k = 384, 10
-    shard = HbmIndexShard(D, a.rows, device="cuda")
-    shard.fill_random(a.rows, seed=1)
-    q = torch.nn.functional.normalize(torch.randn(a.nq, D, device="cuda"), dim=-1).bfloat16()
-    h = hip()
-    n = shard.visible
-    ms, sample = shard._block_sample(n)
-    pre_s, _ = shard._scan(ms, q, 16, k, None, None, sample, "bf16")
-    thr = pre_s[:, k - 1].contiguous() - shard.MQ_THR_MARGIN
-    n_qblk = math.ceil(a.nq / h.mq_queries_per_blk(a.sets, a.rsplit))
-    ncu = torch.cuda.get_device_properties(0).multi_processor_count
-    n_rblk = max(1, round(ncu / n_qblk))
-    rpb = _round_up(math.ceil(n / n_rblk), TILE_ROWS)
-    n_rblk = math.ceil(n / rpb)
-    cap = shard.MQ_CAP
-    cs = torch.zeros(a.nq, cap, device="cuda")
-    ci = torch.empty(a.nq, cap, dtype=torch.int32, device="cuda")
-    cnt = torch.empty(a.nq, dtype=torch.int32, device="cuda")
-    st = stream_handle()
-
-    def run(abl):
-        h.index_scan_mq_ablate(shard.rows.data_ptr(), n, rpb, n_rblk, q.data_ptr(), a.nq,
-                               thr.data_ptr(), cs.data_ptr(), ci.data_ptr(), cnt.data_ptr(), cap,
-                               1, st, abl, a.sets, a.rsplit)
-    variants = {f"abl{m}": (lambda m=m: run(m)) for m in (0, 1, 2, 4)}
-    flat = shard.rows[:n].view(torch.int64)
-    variants["torch_int64_sum"] = lambda: flat.sum()   # plain streaming read of the same bytes
-    r = ab(variants, rounds=a.rounds, iters=a.iters)
-    flop = 2 * n * D * a.nq
-    out = {nm: dict(ms=round(m, 3), TFLOPs=round(flop / (m / 1e3) / 1e12),
-                    TBps=round(n * D * 2 / (m / 1e3) / 1e12, 2)) for nm, (m, _) in r.items()}
-    timeit(lambda: run(3), 10)
-    run(3)
-    torch.cuda.synchronize()
-    st_ = cs.view(-1)[: 2 * n_rblk * n_qblk].view(-1, 2).double()
-    ghz = (st_[:, 0] / st_[:, 1] * 0.1).median().item()
-    out["in_kernel_clock_GHz"] = round(ghz, 3)
-    out["cycles_per_tile"] = round((st_[:, 0] / math.ceil(rpb / TILE_ROWS)).median().item(), 1)
-    print(json.dumps({"bench": "scanmq_ablation", "rows": n, "nq": a.nq, "sets": a.sets, "rsplit": a.rsplit,
-                      "n_rblk": n_rblk, "n_qblk": n_qblk, "results": out}))
-
-
-def cmd_scanabl(a):
-    """DMA-only vs compute-only vs full scan (D=384), plus a plain torch streaming read."""
-    from codename_symbiont_amd.index.shard import HbmIndexShard, _round_up
-    from codename_symbiont_amd.ops._ext import hip, stream_handle
-
-    D = 384
-    shard = HbmIndexShard(D, a.rows, device="cuda")
-    shard.fill_random(a.rows, seed=1)
-    q = torch.nn.functional.normalize(torch.randn(a.nq, D, device="cuda"), dim=-1).bfloat16()
-    h = hip()
-    n_qblk = math.ceil(a.nq / 256)
-    ncu = torch.cuda.get_device_properties(0).multi_processor_count
-    n_rblk = max(1, round(ncu / n_qblk))
-    rpb = _round_up(math.ceil(a.rows / n_rblk), 64)
-    n_rblk = math.ceil(a.rows / rpb)
-    cs = torch.empty(a.nq, n_rblk * 2 * 16, device="cuda")
-    ci = torch.empty(a.nq, n_rblk * 2 * 16, dtype=torch.int32, device="cuda")
-    st = stream_handle()
-    flat = shard.rows[:a.rows].view(torch.int64)
-    pre_s, _ = shard._scan(a.rows // 64, q, 16, 10, None, None)
-    thr = torch.nextafter(pre_s[:, 9].contiguous(), torch.tensor(-math.inf, device="cuda"))
-    tp = thr.data_ptr() if a.seed else 0
-    variants = {f"abl{m}": (lambda m=m: h.index_scan_ablate(shard.rows.data_ptr(), a.rows, rpb, n_rblk,
-                                                            q.data_ptr(), a.nq, cs.data_ptr(),
-                                                            ci.data_ptr(), st, m, tp)) for m in (0, 1, 2, 3, 4, 5)}
-    variants["torch_int64_sum"] = lambda: flat.sum()
-    # correctness: the 8-wave (abl0) and the wide 4-wave (abl3) kernels give the same merged top-k
-    merged = {}
-    for m in (0, 3, 4):
-        variants[f"abl{m}"]()
-        os_ = torch.empty(a.nq, 10, device="cuda")
-        oi = torch.empty(a.nq, 10, dtype=torch.int32, device="cuda")
-        h.topk_merge(cs.data_ptr(), ci.data_ptr(), a.nq, n_rblk * 2 * 16, 16, 10,
-                     os_.data_ptr(), oi.data_ptr(), 0, 0, st)
-        torch.cuda.synchronize()
-        merged[m] = (os_.clone(), oi.clone())
-    same_var = {m: bool(torch.equal(merged[0][1], merged[m][1])) for m in (3, 4)}
-    r = ab(variants, rounds=a.rounds, iters=a.iters)
-    out = {k: dict(ms=round(m, 3), GBps=round(a.rows * D * 2 / (m / 1e3) / 1e9)) for k, (m, _) in r.items()}
-    print(json.dumps({"bench": "scan_ablation", "rows": a.rows, "nq": a.nq, "seeded": bool(a.seed), "variants_match_abl0": same_var,
-                      "results": out}))
-
-
-def cmd_scanstamp(a):
-    """Per-segment s_memtime stamps of the D=384 scan (diagnostic builds: full, L2-source, compute)."""
-    from codename_symbiont_amd.index.shard import HbmIndexShard, _round_up
-    from codename_symbiont_amd.ops._ext import hip, stream_handle
-
-    D = 384
-    shard = HbmIndexShard(D, a.rows, device="cuda")
-    shard.fill_random(a.rows, seed=1)
-    q = torch.nn.functional.normalize(torch.randn(a.nq, D, device="cuda"), dim=-1).bfloat16()
-    h = hip()
-    n_rblk = max(1, round(torch.cuda.get_device_properties(0).multi_processor_count / math.ceil(a.nq / 256)))
-    rpb = _round_up(math.ceil(a.rows / n_rblk), 64)
-    n_rblk = math.ceil(a.rows / rpb)
-    cs = torch.zeros(a.nq, n_rblk * 2 * 16, device="cuda")
-    ci = torch.empty(a.nq, n_rblk * 2 * 16, dtype=torch.int32, device="cuda")
-    st = stream_handle()
-    names = ["vmcnt_wait", "barrier", "chain0+dma", "pro1+topk0", "chain1", "topk1", "cyc_per_tile", "GHz"]
-    out = {}
-    pre_s, _ = shard._scan(a.rows // 64, q, 16, 10, None, None)
-    thr = torch.nextafter(pre_s[:, 9].contiguous(), torch.tensor(-math.inf, device="cuda"))
-    for m, label, tp in ((8, "full", 0), (8, "full_seeded", thr.data_ptr()), (9, "l2_source", 0),
-                         (10, "compute_only", 0)):
-        run = lambda: h.index_scan_ablate(shard.rows.data_ptr(), a.rows, rpb, n_rblk, q.data_ptr(), a.nq,
-                                          cs.data_ptr(), ci.data_ptr(), st, m, tp)
-        ms = timeit(run, 20)  # also warms the clock
-        run()
-        torch.cuda.synchronize()
-        v = cs.view(-1)[: n_rblk * 8 * 8].view(n_rblk, 8, 8)
-        med = v.median(dim=0).values  # [wave, seg]
-        out[label] = dict(ms=round(ms, 3), per_wave={f"w{w}": [round(float(x), 1) for x in med[w]] for w in range(8)},
-                          mean={n: round(float(v[:, :, i].mean()), 1) for i, n in enumerate(names)})
-    print(json.dumps({"bench": "scan_stamps", "rows": a.rows, "segments": names, "results": out}))
-
-
 def cmd_scanfp8(a):
     """fp8 (e4m3) index scan, D=1024 by default (BASELINE config #5 geometry), seeded top-10."""
     from codename_symbiont_amd.index.shard import HbmIndexShard
@@ -309,16 +170,12 @@ def cmd_scanfp8(a):
     q = torch.nn.functional.normalize(torch.randn(a.nq, D, device="cuda"), dim=-1).bfloat16()
     out = {}
 
-    def run(variant, seed):
-        shard.scan_variant, shard.seed_threshold = variant, seed
+    def run(seed):
+        shard.seed_threshold = seed
         return shard.search(q, 10)
 
-    ref = run(0, False)
-    vs = (0,)
-    out["variants_match"] = all(torch.equal(ref[1], run(v, sd)[1]) for v in vs for sd in (0, 1))
-    variants = {f"v{v}_seed{sd}": (lambda v=v, sd=sd: run(v, sd)) for v in vs for sd in (False, True)}
-    # v9: the default geometry re-reading 8 tiles per row block from L2 (compute ceiling)
-    variants["v9_l2src_seedTrue"] = lambda: run(9, True)
+    out["seeded_matches_unseeded"] = bool(torch.equal(run(False)[1], run(True)[1]))
+    variants = {f"seed{sd}": (lambda sd=sd: run(sd)) for sd in (False, True)}
     r = ab(variants, rounds=a.rounds, iters=a.iters)
     for k, (med, mn) in r.items():
         out[k] = dict(ms=round(med, 3), GBps=round(a.rows * D / (med / 1e3) / 1e9),
@@ -567,7 +424,7 @@ def cmd_prefilter(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("cmd", choices=["scan", "scanmq", "scanmqabl", "scanabl", "scanstamp", "scanfp8", "gemm", "encoder", "attn", "latency", "gemmfp8", "prefilter"])
+    ap.add_argument("cmd", choices=["scan", "scanmq", "scanfp8", "gemm", "encoder", "attn", "latency", "gemmfp8", "prefilter"])
     ap.add_argument("--qmode", choices=["random", "near"], default="random", help="prefilter: query kind")
     ap.add_argument("--rows", type=int, default=100_000_000)
     ap.add_argument("--dim", type=int, default=384)
@@ -576,22 +433,19 @@ def main():
     ap.add_argument("--seq", type=int, default=128)
     ap.add_argument("--head-dim", type=int, default=32)
     ap.add_argument("--model", default="minilm-l6")
-    ap.add_argument("--seed", type=int, default=1, help="scanabl: seed per-query thresholds")
     ap.add_argument("--precision", default="bf16", help="encoder: comma list of bf16,fp8")
     ap.add_argument("--mlp", default="1", help="encoder: comma list of mlp_fused_config values "
                     "(1: the fused 384-wide FFN block, 2: + the out-projection, 0: two GEMMs)")
     ap.add_argument("--tiles", default="3", help="encoder: comma list of gemm_config tile modes "
                     "(3 = the default auto tiles, 10 = round-3 auto, 12 = round-3 default with hipBLASLt)")
     ap.add_argument("--fp8-waves", default="8", help="encoder: comma list of fp8 GEMM wave counts")
-    ap.add_argument("--sets", type=int, default=4, help="scanmqabl: 16-query sets per wave (2 or 4)")
-    ap.add_argument("--rsplit", type=int, default=1, help="scanmqabl: waves per query group (1, 2)")
     ap.add_argument("--prune", action="store_true", help="scanmq: also the exact int8-pruned search")
     ap.add_argument("--prune-shift", type=int, default=0,
                     help="scanmq --prune: threshold sample 1 tile in 2^shift (0 = shard default)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=5)
     a = ap.parse_args()
-    {"scan": cmd_scan, "scanmq": cmd_scanmq, "scanmqabl": cmd_scanmqabl, "scanabl": cmd_scanabl, "scanstamp": cmd_scanstamp, "scanfp8": cmd_scanfp8, "gemm": cmd_gemm, "encoder": cmd_encoder, "attn": cmd_attn, "latency": cmd_latency, "gemmfp8": cmd_gemmfp8, "prefilter": cmd_prefilter}[a.cmd](a)
+    {"scan": cmd_scan, "scanmq": cmd_scanmq, "scanfp8": cmd_scanfp8, "gemm": cmd_gemm, "encoder": cmd_encoder, "attn": cmd_attn, "latency": cmd_latency, "gemmfp8": cmd_gemmfp8, "prefilter": cmd_prefilter}[a.cmd](a)
 
 
 if __name__ == "__main__":

@@ -351,7 +351,6 @@ class HbmIndexShard:
         # but unwritten row (stream order then guarantees the write lands first)
         self.visible = 0
         self.payloads = PayloadStore()
-        self.scan_ns = 0     # LDS ring depth of the fused scan (0 = kernel default)
         # smallest row block (in 64-row tiles) of the 256-query list scan: small scans (threshold
         # seeding, the fresh-row tail) are latency-bound, so fewer tiles per block = more CUs
         self.scan_min_tiles = 16
@@ -364,7 +363,6 @@ class HbmIndexShard:
         # masked search (_search_filtered): a stride-64 pass over the live tiles first, whose k-th
         # best allowed score seeds the full pass's thresholds (FILTER_SEED_DEFAULT has the A/B)
         self.filter_seed = self.FILTER_SEED_DEFAULT
-        self.scan_variant = 0        # fp8 scan ring geometry (0 = default)
         # > 256 queries: put the query blocks of each row block on one XCD (row stream shared
         # through that XCD's L2 instead of re-read from HBM once per query block)
         self.scan_xcd = 1
@@ -1893,11 +1891,11 @@ class HbmIndexShard:
         if dtype == "fp8":
             h.index_scan_fp8(rows.data_ptr(), n, self.dim, rows_per_blk, n_rblk,
                              q_unit.data_ptr(), NQ, kmax, cs.data_ptr(), ci.data_ptr(), st,
-                             self.scan_aux, thr_p, self.scan_variant, self.scan_xcd)
+                             self.scan_aux, thr_p, self.scan_xcd)
         else:
             h.index_scan(rows.data_ptr(), n, self.dim, rows_per_blk, n_rblk, q_unit.data_ptr(),
-                         NQ, kmax, cs.data_ptr(), ci.data_ptr(), st, self.scan_ns, self.scan_aux,
-                         thr_p, self.scan_xcd, gate_p)
+                         NQ, kmax, cs.data_ptr(), ci.data_ptr(), st, self.scan_aux, thr_p,
+                         self.scan_xcd, gate_p)
         h.topk_merge(cs.data_ptr(), ci.data_ptr(), NQ, ncand, kmax, k, out_s.data_ptr(),
                      out_i.data_ptr(), 0, 0, st, gate_p)
         return out_s, out_i

@@ -51,11 +51,7 @@ int symb_qkv_attention(const void* X, const void* Wqkv, const float* bqkv, const
 static int g_qkv_attn = 1;
 int symb_index_scan(const void* X, int n_valid, int D, int rows_per_blk, int n_rblk,
                     const void* Q, int NQ, int kmax, float* cand_s, int* cand_i, hipStream_t st,
-                    int ns, int aux, const float* thr_init, int xcd,
-                    const int* gate = nullptr);
-int symb_index_scan_ablate(const void* X, int n_valid, int rows_per_blk, int n_rblk,
-                           const void* Q, int NQ, float* cs, int* ci, hipStream_t st, int abl,
-                           const float* thr);
+                    int aux, const float* thr_init, int xcd, const int* gate = nullptr);
 int symb_gemm_config(int resln_bm, int tile, int group_m);
 int symb_gemm_fp8_config(int waves, int big);
 int symb_gemm_resln_config(int waves);
@@ -79,7 +75,7 @@ int symb_quant_fp8(const void* in, int in_f32, int ld_in, uint8_t* out, int ld_o
                    float scale, int normalize, hipStream_t st);
 int symb_index_scan_fp8(const void* X, int n_valid, int D, int rows_per_blk, int n_rblk,
                         const void* Q, int NQ, int kmax, float* cand_s, int* cand_i,
-                        hipStream_t st, int aux, const float* thr_init, int variant, int xcd);
+                        hipStream_t st, int aux, const float* thr_init, int xcd);
 int symb_topk_merge(const float* cand_s, const int* cand_i, int NQ, int n_cand_per_query,
                     int kmax, int k, float* out_s, int* out_i, int64_t id_offset,
                     int64_t* out_id64, hipStream_t st, const int* gate = nullptr);
@@ -166,16 +162,11 @@ int symb_gemm_skinny_max_m();
 int symb_gemm_skinny_nw8(int max_kg, int min_wgs);
 size_t symb_gemm_skinny_scratch_bytes(int epi, int M, int N, int K);
 void symb_gemm_skinny_set_scratch(void* p, size_t bytes);
-int symb_mq_config(int aux);
 int symb_index_scan_mq(const void* X, int n_valid, int rows_per_blk, int n_rblk, const void* Q,
                        int NQ, const float* thr, float* cand_s, int* cand_i, int* cand_n, int cap,
                        int xcd, hipStream_t st, int sets, int tshift, int rsplit,
                        const int* gate, const int* blist, int list_tiles, int zero_cnt, int dim);
 int symb_mq_max_sets(int dim);
-int symb_index_scan_mq_ablate(const void* X, int n_valid, int rows_per_blk, int n_rblk,
-                              const void* Q, int NQ, const float* thr, float* cand_s, int* cand_i,
-                              int* cand_n, int cap, int xcd, hipStream_t st, int abl, int sets,
-                              int rsplit);
 int symb_prune_stats(const int* ovf, const int* cnt, int NQ, const int* dense, const int* blk,
                      int* tot, hipStream_t st);
 int symb_topk_select_counted(const float* cand_s, const int* cand_i, const int* cand_n, int cap,
@@ -589,16 +580,16 @@ PYBIND11_MODULE(_hip, m) {
     return py::make_tuple(lists, qpb);
   });
   m.def("index_scan", [](uptr X, int n_valid, int D, int rows_per_blk, int n_rblk, uptr Q, int NQ,
-                         int kmax, uptr cand_s, uptr cand_i, uptr st, int ns, int aux, uptr thr,
-                         int xcd, uptr gate) {
+                         int kmax, uptr cand_s, uptr cand_i, uptr st, int aux, uptr thr, int xcd,
+                         uptr gate) {
     check(symb_index_scan(P<void>(X), n_valid, D, rows_per_blk, n_rblk, P<void>(Q), NQ, kmax,
-                          P<float>(cand_s), P<int>(cand_i), S(st), ns, aux, P<const float>(thr),
-                          xcd, P<const int>(gate)),
+                          P<float>(cand_s), P<int>(cand_i), S(st), aux, P<const float>(thr), xcd,
+                          P<const int>(gate)),
           "index_scan");
   }, py::arg("X"), py::arg("n_valid"), py::arg("D"), py::arg("rows_per_blk"), py::arg("n_rblk"),
      py::arg("Q"), py::arg("NQ"), py::arg("kmax"), py::arg("cand_s"), py::arg("cand_i"),
-     py::arg("stream"), py::arg("ns") = 0, py::arg("aux") = -1, py::arg("thr_init") = 0,
-     py::arg("xcd") = 1, py::arg("gate") = 0);
+     py::arg("stream"), py::arg("aux") = -1, py::arg("thr_init") = 0, py::arg("xcd") = 1,
+     py::arg("gate") = 0);
   // multi-query-block D=384 scan (index_mq.hip): candidates above the seeded thresholds
   m.def("i8_queries_per_blk", [](int rsplit) { return symb_i8_queries_per_blk(rsplit); },
         py::arg("rsplit") = 2);
@@ -785,7 +776,6 @@ PYBIND11_MODULE(_hip, m) {
   m.def("gemm_lt_config", [](int mode) { check(symb_gemm_lt_config(mode), "gemm_lt_config"); },
         py::arg("mode"));
   m.def("gemm_lt_plans", []() { return symb_gemm_lt_plans(); });
-  m.def("mq_config", [](int aux) { check(symb_mq_config(aux), "mq_config"); }, py::arg("aux"));
   m.def("mq_queries_per_blk", [](int sets, int rsplit) { return symb_mq_queries_per_blk(sets, rsplit); },
         py::arg("sets") = 4, py::arg("rsplit") = 1);
   m.def("index_scan_mq", [](uptr X, int n_valid, int rows_per_blk, int n_rblk, uptr Q, int NQ,
@@ -803,17 +793,6 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("tshift") = 0, py::arg("rsplit") = 1, py::arg("gate") = 0, py::arg("blist") = 0,
      py::arg("list_tiles") = 0, py::arg("zero_cnt") = true, py::arg("dim") = 384);
   m.def("mq_max_sets", [](int dim) { return symb_mq_max_sets(dim); }, py::arg("dim"));
-  m.def("index_scan_mq_ablate", [](uptr X, int n_valid, int rows_per_blk, int n_rblk, uptr Q,
-                                   int NQ, uptr thr, uptr cand_s, uptr cand_i, uptr cand_n,
-                                   int cap, int xcd, uptr st, int abl, int sets, int rsplit) {
-    check(symb_index_scan_mq_ablate(P<void>(X), n_valid, rows_per_blk, n_rblk, P<void>(Q), NQ,
-                                    P<const float>(thr), P<float>(cand_s), P<int>(cand_i),
-                                    P<int>(cand_n), cap, xcd, S(st), abl, sets, rsplit),
-          "index_scan_mq_ablate");
-  }, py::arg("X"), py::arg("n_valid"), py::arg("rows_per_blk"), py::arg("n_rblk"), py::arg("Q"),
-     py::arg("NQ"), py::arg("thr"), py::arg("cand_s"), py::arg("cand_i"), py::arg("cand_n"),
-     py::arg("cap"), py::arg("xcd"), py::arg("stream"), py::arg("abl"), py::arg("sets") = 4,
-     py::arg("rsplit") = 1);
   m.def("prune_stats", [](uptr ovf, uptr cnt, int NQ, uptr dense, uptr blk, uptr tot, uptr st) {
     check(symb_prune_stats(P<const int>(ovf), P<const int>(cnt), NQ, P<const int>(dense),
                            P<const int>(blk), P<int>(tot), S(st)),
@@ -837,14 +816,6 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("stream"), py::arg("gate") = 0, py::arg("reset_ovf") = true, py::arg("ld") = 0,
      py::arg("kth_out") = 0, py::arg("kth_margin") = 0.f, py::arg("seg2_s") = 0,
      py::arg("seg2_cap") = 0, py::arg("seg2_out_s") = 0, py::arg("seg2_out_i") = 0);
-  m.def("index_scan_ablate", [](uptr X, int n_valid, int rows_per_blk, int n_rblk, uptr Q, int NQ,
-                                uptr cs, uptr ci, uptr st, int abl, uptr thr) {
-    check(symb_index_scan_ablate(P<void>(X), n_valid, rows_per_blk, n_rblk, P<void>(Q), NQ,
-                                 P<float>(cs), P<int>(ci), S(st), abl, P<const float>(thr)),
-          "index_scan_ablate");
-  }, py::arg("X"), py::arg("n_valid"), py::arg("rows_per_blk"), py::arg("n_rblk"), py::arg("Q"),
-     py::arg("NQ"), py::arg("cs"), py::arg("ci"), py::arg("stream"), py::arg("abl"),
-     py::arg("thr") = 0);
   m.def("attention_config", [](int waves, int kvt, int xcd) {
     check(symb_attention_config(waves, kvt, xcd), "attention_config");
   }, py::arg("waves") = 8, py::arg("kvt") = 64, py::arg("xcd") = 2);
@@ -899,15 +870,14 @@ PYBIND11_MODULE(_hip, m) {
   });
   m.def("index_scan_fp8", [](uptr X, int n_valid, int D, int rows_per_blk, int n_rblk, uptr Q,
                              int NQ, int kmax, uptr cand_s, uptr cand_i, uptr st, int aux, uptr thr,
-                             int variant, int xcd) {
+                             int xcd) {
     check(symb_index_scan_fp8(P<void>(X), n_valid, D, rows_per_blk, n_rblk, P<void>(Q), NQ, kmax,
                               P<float>(cand_s), P<int>(cand_i), S(st), aux, P<const float>(thr),
-                              variant, xcd),
+                              xcd),
           "index_scan_fp8");
   }, py::arg("X"), py::arg("n_valid"), py::arg("D"), py::arg("rows_per_blk"), py::arg("n_rblk"),
      py::arg("Q"), py::arg("NQ"), py::arg("kmax"), py::arg("cand_s"), py::arg("cand_i"),
-     py::arg("stream"), py::arg("aux") = -1, py::arg("thr_init") = 0, py::arg("variant") = 0,
-     py::arg("xcd") = 1);
+     py::arg("stream"), py::arg("aux") = -1, py::arg("thr_init") = 0, py::arg("xcd") = 1);
   m.def("filter_tiles", [](uptr mask, int n_words, int n_valid, uptr blk_cnt, uptr tiles,
                            uptr n_live, uptr st) {
     check(symb_filter_tiles(P<void>(mask), n_words, n_valid, P<int>(blk_cnt), P<int>(tiles),

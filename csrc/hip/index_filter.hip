@@ -145,11 +145,7 @@ __global__ __launch_bounds__(512) void index_scan_filter_kernel(
   const int query = qb * (QW * TOPK_WAVES) + wave * QW + qlocal;
   const __bf16* qp = Q + (size_t)min(query, NQ - 1) * D;
   bf16x8 qf[NKS];
-#pragma unroll
-  for (int ks = 0; ks < NKS; ++ks) {
-    const int k0 = MFMA_32 ? ks * 16 + (lane >> 5) * 8 : ks * 32 + (lane >> 4) * 8;
-    qf[ks] = *reinterpret_cast<const bf16x8*>(qp + k0);
-  }
+  load_query_frags<D, MFMA_32>(qf, qp, lane);
 
   // ---- per-thread DMA source offsets within an interval (identical for every interval) ----
   uint32_t goff[LOADS];
@@ -189,9 +185,8 @@ __global__ __launch_bounds__(512) void index_scan_filter_kernel(
   }
   // thr_init[q] (optional): a lower bound on query q's final k-th ALLOWED score
   float thr = thr_init ? thr_init[min(query, NQ - 1)] : -INFINITY;
-  // row of accumulator register r within the sub-tile = lane_row + reg_row(r)
+  // row of accumulator register r within the sub-tile = lane_row + acc_reg_row(r)
   const int lane_row = MFMA_32 ? 4 * (lane >> 5) : 4 * (lane >> 4);
-  auto reg_row = [](int r) { return MFMA_32 ? (r & 3) + 8 * (r >> 2) : r; };
   // bits: the sub-tile's SUB mask bits (wave-uniform), bit j = row row0 + j allowed
   auto topk_update = [&](Acc& acc, int row0, uint32_t bits) {
     constexpr uint32_t FULL = MFMA_32 ? 0xffffffffu : 0xffffu;
@@ -199,7 +194,7 @@ __global__ __launch_bounds__(512) void index_scan_filter_kernel(
       const uint32_t lbits = bits >> lane_row;
 #pragma unroll
       for (int r = 0; r < NR; ++r)
-        if (!((lbits >> reg_row(r)) & 1u)) acc[r] = -INFINITY;
+        if (!((lbits >> acc_reg_row<MFMA_32>(r)) & 1u)) acc[r] = -INFINITY;
     }
     float mx = acc[0];
 #pragma unroll
@@ -210,9 +205,9 @@ __global__ __launch_bounds__(512) void index_scan_filter_kernel(
         if (acc[r] > thr) {
           // (KMAX = 32: the in-place form; the parallel one's second copy of the list spills)
           if constexpr (KMAX > 16)
-            topk_insert<KMAX>(tv, ti, acc[r], row0 + lane_row + reg_row(r));
+            topk_insert<KMAX>(tv, ti, acc[r], row0 + lane_row + acc_reg_row<MFMA_32>(r));
           else
-            topk_insert_par<KMAX>(tv, ti, acc[r], row0 + lane_row + reg_row(r));
+            topk_insert_par<KMAX>(tv, ti, acc[r], row0 + lane_row + acc_reg_row<MFMA_32>(r));
           thr = fmaxf(thr, tv[KMAX - 1]);
         }
       }

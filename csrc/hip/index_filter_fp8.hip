@@ -129,14 +129,14 @@ __global__ __launch_bounds__(256, 1) void index_scan_filter_fp8_kernel(
   // thr_init[q] (optional): a lower bound on query q's final k-th ALLOWED score, raw units
   float thr0 = thr_init ? thr_init[min(query0, NQ - 1)] : -INFINITY;
   float thr1 = thr_init ? thr_init[min(query1, NQ - 1)] : -INFINITY;
-  // row of accumulator register r within the 32-row sub-tile = 4 h + (r & 3) + 8 (r >> 2), for
+  // row of accumulator register r within the 32-row sub-tile = 4 h + acc_reg_row(r), for
   // both query sets; bits: the sub-tile's 32 mask bits (wave-uniform), bit j = row j allowed
   auto mask_rows = [&](f32x16& a0, f32x16& a1, uint32_t bits) {
     if (bits != 0xffffffffu) {
       const uint32_t lbits = bits >> (4 * h);
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (!((lbits >> ((r & 3) + 8 * (r >> 2))) & 1u)) {
+        if (!((lbits >> acc_reg_row<true>(r)) & 1u)) {
           a0[r] = -INFINITY;
           a1[r] = -INFINITY;
         }
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256, 1) void index_scan_filter_fp8_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         if (acc[r] > thr) {
-          topk_insert_par<KMAX>(tv, ti, acc[r], rb4 + (r & 3) + 8 * (r >> 2));
+          topk_insert_par<KMAX>(tv, ti, acc[r], rb4 + acc_reg_row<true>(r));
           thr = fmaxf(thr, tv[KMAX - 1]);
         }
       }

@@ -65,12 +65,9 @@ __global__ __launch_bounds__(256) void quant_fp8_kernel(const void* __restrict__
 }
 
 // ---- scan (fragment pipeline, swizzle and ring geometry: fp8_scan.h) ---------------------------
-// DIAG (timing diagnostics only -- results are not a search's): DG_L2 every tile re-reads the
-// block's first 8 tiles (an L2-resident source); DG_NODMA no loads after the prologue (stale
-// LDS); DG_NOUPD no top-k test; DG_NOBAR no per-tile barrier.
-enum { DG_L2 = 1, DG_NODMA = 2, DG_NOUPD = 4, DG_NOBAR = 8 };
-
-template <int D, int KMAX, int NS, int SUBS, int AUX, int DIAG = 0>
+// (The timing diagnostics this kernel carried -- L2-resident source, no loads, no top-k test, no
+// barrier -- are retired; what they measured is in profiles/r6_fp8.)
+template <int D, int KMAX, int NS, int SUBS, int AUX>
 __global__ __launch_bounds__(256, 1) void index_scan_fp8_kernel(
     const uint8_t* __restrict__ X, int n_valid, int rows_per_blk, const uint8_t* __restrict__ Q,
     int NQ, int n_qblk, int xcd, const float* __restrict__ thr_init, float* __restrict__ cand_s,
@@ -121,7 +118,7 @@ __global__ __launch_bounds__(256, 1) void index_scan_fp8_kernel(
   }
   auto issue_piece = [&](int t, int i) {
     // past the end: re-load the last tile (keeps vmcnt exact)
-    const int tt = (DIAG & DG_L2) ? (t & 7) % n_tiles : min(t, n_tiles - 1);
+    const int tt = min(t, n_tiles - 1);
     const uint8_t* base = X + (size_t)(row_begin + tt * TR) * D;
     char* dst = smem + (t % NS) * TILE_BYTES;
     glds16_aux<AUX>(base + (size_t)(i / GP) * (GP * RPS * D) + goff[i % GP],
@@ -147,6 +144,8 @@ __global__ __launch_bounds__(256, 1) void index_scan_fp8_kernel(
   }
   float thr0 = thr_init ? thr_init[min(query0, NQ - 1)] : -INFINITY;
   float thr1 = thr_init ? thr_init[min(query1, NQ - 1)] : -INFINITY;
+  // (rows below: rb4 + acc_reg_row<true>(r), scan_common.h, spelled out -- through the helper
+  // every instantiation of this kernel schedules its prologue differently)
   auto update = [&](f32x16& acc, float (&tv)[KMAX], int (&ti)[KMAX], float& thr, int row0) {
     const int rb4 = row0 + 4 * h;
     if (row0 + SUB > row_end) {
@@ -176,10 +175,8 @@ __global__ __launch_bounds__(256, 1) void index_scan_fp8_kernel(
   i32x4 lo[R], hi[R];
   for (int t = 0; t < n_tiles; ++t) {
     wait_vmcnt<LOADS * (NS - 2)>();  // tile t landed for this wave
-    if constexpr (!(DIAG & DG_NOBAR)) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
     const uint32_t tbase = lds_smem + (uint32_t)((t % NS) * TILE_BYTES);
     const int row0 = row_begin + t * TR;
     const int tnext = t + NS - 1;
@@ -190,10 +187,7 @@ __global__ __launch_bounds__(256, 1) void index_scan_fp8_kernel(
       f32x16 acc0, acc1;
       if (sub == 0) {
         fp8_prologue<0, PF, R, G>(lo, hi, voff, base);
-        if constexpr (DIAG & DG_NODMA)
-          Fp8Chain<0, NKS, PF, 0, G>::run(acc0, acc1, lo, hi, q0, q1, voff, base, NoDma());
-        else
-          Fp8Chain<0, NKS, PF, LOADS, G>::run(acc0, acc1, lo, hi, q0, q1, voff, base, dma);
+        Fp8Chain<0, NKS, PF, LOADS, G>::run(acc0, acc1, lo, hi, q0, q1, voff, base, dma);
       } else {
         Fp8Chain<0, NKS, PF, 0, G>::run(acc0, acc1, lo, hi, q0, q1, voff, base, NoDma());
       }
@@ -201,10 +195,8 @@ __global__ __launch_bounds__(256, 1) void index_scan_fp8_kernel(
         fp8_prologue<0, PF, R, G>(lo, hi, voff, base + SUB_BYTES);
       // (reads of the asm MFMA results stay below the chain-end s_nops: index_i8.hip emit)
       asm volatile("" : "+v"(acc0), "+v"(acc1));
-      if constexpr (!(DIAG & DG_NOUPD)) {
-        update(acc0, tv0, ti0, thr0, row0 + sub * SUB);
-        update(acc1, tv1, ti1, thr1, row0 + sub * SUB);
-      }
+      update(acc0, tv0, ti0, thr0, row0 + sub * SUB);
+      update(acc1, tv1, ti1, thr1, row0 + sub * SUB);
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the tail prefetches before exit
@@ -246,41 +238,27 @@ int symb_quant_fp8(const void* in, int in_f32, int ld_in, uint8_t* out, int ld_o
   return (int)hipGetLastError();
 }
 
-template <int D, int KMAX, int NS, int SUBS, int AUX, int DIAG = 0>
+template <int D, int KMAX, int NS, int SUBS, int AUX>
 static int launch_fp8(const void* X, int n_valid, int rows_per_blk, int n_rblk, const void* Q,
                       int NQ, int n_qblk, int xcd, const float* thr, float* cs, int* ci,
                       hipStream_t st) {
-  auto kern = index_scan_fp8_kernel<D, KMAX, NS, SUBS, AUX, DIAG>;
+  auto kern = index_scan_fp8_kernel<D, KMAX, NS, SUBS, AUX>;
   constexpr int lds = NS * 32 * SUBS * D;
-  set_max_lds<index_scan_fp8_kernel<D, KMAX, NS, SUBS, AUX, DIAG>>(lds);
+  set_max_lds<index_scan_fp8_kernel<D, KMAX, NS, SUBS, AUX>>(lds);
   hipLaunchKernelGGL(kern, dim3(n_rblk * n_qblk), dim3(256), lds, st, (const uint8_t*)X, n_valid,
                      rows_per_blk, (const uint8_t*)Q, NQ, n_qblk, xcd, thr, cs, ci);
   return (int)hipGetLastError();
 }
 
 template <int D>
-static int dispatch_fp8(int kmax, int aux, int variant, const void* X, int n_valid,
-                        int rows_per_blk, int n_rblk, const void* Q, int NQ, int n_qblk, int xcd,
-                        const float* thr, float* cs, int* ci, hipStream_t st) {
+static int dispatch_fp8(int kmax, int aux, const void* X, int n_valid, int rows_per_blk,
+                        int n_rblk, const void* Q, int NQ, int n_qblk, int xcd, const float* thr,
+                        float* cs, int* ci, hipStream_t st) {
   constexpr int SUBS = Fp8Cfg<D>::SUBS, NS = Fp8Cfg<D>::NS;
 #define SYMB_F(K, NS_, SUBS_, A) \
   launch_fp8<D, K, NS_, SUBS_, A>(X, n_valid, rows_per_blk, n_rblk, Q, NQ, n_qblk, xcd, thr, cs, ci, st)
   // (round 6: one sub-tile per barrier with a 4- or 5-deep ring measured 4 % slower at 100M x
-  // 1024 -- profiles/r6_fp8/ -- and was removed.)  Variants 9-14 (D = 1024): timing diagnostics
-  // of the default geometry, not search results -- 9 L2-resident source, 11 no loads after the
-  // prologue, 12 no top-k test, 13 no barrier, 14 = 11 + 12 + 13 (the bare MFMA chains)
-  if constexpr (D == 1024) {
-#define SYMB_DG(DG) launch_fp8<D, 16, NS, SUBS, 0, DG>(X, n_valid, rows_per_blk, n_rblk, Q, NQ, \
-                                                      n_qblk, xcd, thr, cs, ci, st)
-    switch (variant) {
-      case 9: return SYMB_DG(DG_L2);
-      case 11: return SYMB_DG(DG_NODMA);
-      case 12: return SYMB_DG(DG_NOUPD);
-      case 13: return SYMB_DG(DG_NOBAR);
-      case 14: return SYMB_DG(DG_NODMA | DG_NOUPD | DG_NOBAR);
-    }
-#undef SYMB_DG
-  }
+  // 1024 -- profiles/r6_fp8/ -- and was removed.)
   if (kmax == 16) return aux ? SYMB_F(16, NS, SUBS, 2) : SYMB_F(16, NS, SUBS, 0);
   if (kmax == 32) return aux ? SYMB_F(32, NS, SUBS, 2) : SYMB_F(32, NS, SUBS, 0);
 #undef SYMB_F
@@ -289,15 +267,14 @@ static int dispatch_fp8(int kmax, int aux, int variant, const void* X, int n_val
 
 // X: [>= round_up(n_valid, 64), D] e4m3 rows (scale S), Q: [NQ, D] e4m3 queries (scale S).
 // Candidates: [NQ][n_rblk][2][kmax] raw accumulators (S^2 * cosine); thr_init in the same units.
-// variant: 0 = the ring geometry of Fp8Cfg; 9, 11-14 (D = 1024) = timing diagnostics.
 int symb_index_scan_fp8(const void* X, int n_valid, int D, int rows_per_blk, int n_rblk,
                         const void* Q, int NQ, int kmax, float* cand_s, int* cand_i,
-                        hipStream_t st, int aux, const float* thr_init, int variant, int xcd) {
+                        hipStream_t st, int aux, const float* thr_init, int xcd) {
   if (NQ <= 0 || n_rblk <= 0) return 0;
   if (rows_per_blk % 64) return -1;
   const int n_qblk = (NQ + 255) / 256;
   if (aux < 0) aux = n_qblk == 1 ? 2 : 0;
-#define SYMB_ARGS kmax, aux, variant, X, n_valid, rows_per_blk, n_rblk, Q, NQ, n_qblk, xcd, thr_init, \
+#define SYMB_ARGS kmax, aux, X, n_valid, rows_per_blk, n_rblk, Q, NQ, n_qblk, xcd, thr_init, \
                   cand_s, cand_i, st
   switch (D) {
     case 256: return dispatch_fp8<256>(SYMB_ARGS);

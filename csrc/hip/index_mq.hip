@@ -142,10 +142,9 @@ __device__ __forceinline__ void mq_prologue(bf16x8 (&a)[mq::R], uint32_t base) {
 // thr[NQ]: per-query lower bounds on the final k-th score (required).
 // cand_s/cand_i: [NQ][cap]; cand_n[NQ] (zeroed): number of candidates each query emitted (may
 // exceed cap: the select kernel then raises the overflow flag).
-// ABL (profiling entry symb_index_scan_mq_ablate only): 1 = no LDS-DMA (compute on whatever the
-// ring holds), 2 = no emission test, 3 = full kernel + per-workgroup s_memtime / s_memrealtime
-// around the tile loop written to cand_s[2 * blockIdx.x + {0, 1}] (in-kernel clock), 4 = LDS-DMA
-// ring only (same waits and barriers, no MFMA chains, no emission test: the row stream's rate).
+// (The kernel's profiling forms -- no LDS-DMA, no emission test, in-kernel clocks, LDS-DMA ring
+// only -- and the non-temporal row stream that measured slower are retired: profiles/r2_mq,
+// profiles/r2_rsplit.)
 //
 // RSPLIT = 2 (the 256-query form of the 1-GPU shape): waves w and w + 4 hold the SAME 64 queries
 // (4 sets) and split each tile's rows, w the first two 16-row sub-tiles and w + 4 the last two.
@@ -153,7 +152,6 @@ __device__ __forceinline__ void mq_prologue(bf16x8 (&a)[mq::R], uint32_t base) {
 // the LDS fragment reads per tile (192 KiB instead of 384) and the chain ends per MFMA, at the
 // same MFMA cycles per SIMD: at 256 queries the scan is bound by the chip's power limit (HBM
 // streaming + MFMAs hold the in-kernel clock near 1.5 GHz), so bytes moved per FLOP count.
-// AUX: cache policy bits of the row stream's LDS-DMA (0 = default, 2 = non-temporal).
 // MqList (block-list mode, blist != nullptr): scan only the row blocks that the pruned search's
 // route sent to the bf16 path (prune_route_kernel, index_i8.hip) instead of rows [0, n_valid).
 // blist[0] = nl listed blocks, blist[1] = the int8 scan's block count, blist[2 + i] = the i-th
@@ -168,7 +166,7 @@ struct MqList {
   int list_tiles;
 };
 
-template <int D, int NSET, int ABL = 0, int RSPLIT = 1, int AUX = 0>
+template <int D, int NSET, int RSPLIT>
 __global__ __launch_bounds__(512, 1) void index_scan_mq_kernel(
     const __bf16* __restrict__ X, int n_valid, int rows_per_blk, const __bf16* __restrict__ Q,
     int NQ, int n_qblk, int xcd, const float* __restrict__ thr_in, float* __restrict__ cand_s,
@@ -259,7 +257,7 @@ __global__ __launch_bounds__(512, 1) void index_scan_mq_kernel(
     const int prow = phys_tile(row_begin / TR + tt) * TR;
     const char* base = reinterpret_cast<const char*>(X + (size_t)(prow + j * SUB) * D + ks * 32);
     char* dst = smem + (t % NS) * TILE_BYTES + p * PIECE;
-    glds16_aux<AUX>(mq_uniform(base) + loff, dst);
+    glds16_aux<0>(mq_uniform(base) + loff, dst);
   };
 
   // ---- per-lane A-fragment offset within a piece (lane holds X[row r][k 8g..8g+7] of the k-step)
@@ -298,11 +296,6 @@ __global__ __launch_bounds__(512, 1) void index_scan_mq_kernel(
     // hazard recognizer does not see asm MFMAs; index_i8.hip emit has the story)
 #pragma unroll
     for (int s = 0; s < SETS; ++s) asm volatile("" : "+v"(acc[s]));
-    if constexpr (ABL == 2 || ABL == 4) {
-#pragma unroll
-      for (int s = 0; s < SETS; ++s) asm volatile("" ::"v"(acc[s]));
-      return;
-    }
     if (row0 + SUB > row_end) {   // last tile of the block: mask rows past its end
       const int rl = row0 + 4 * (lane >> 4);
 #pragma unroll
@@ -349,7 +342,7 @@ __global__ __launch_bounds__(512, 1) void index_scan_mq_kernel(
     }
   };
 
-  if (n_tiles > 0 && ABL != 1) {
+  if (n_tiles > 0) {
 #pragma unroll
     for (int p = 0; p < NS - 1; ++p)
 #pragma unroll
@@ -363,30 +356,18 @@ __global__ __launch_bounds__(512, 1) void index_scan_mq_kernel(
   // test apart and each test overlaps the other wave's chain.
   const bool late = wave_u >= WAVES / 2;
   int prow_last = 0;   // physical first row of the previous tile
-  uint64_t c0 = 0, r0t = 0;
-  if constexpr (ABL == 3) {
-    c0 = __builtin_amdgcn_s_memtime();
-    r0t = __builtin_amdgcn_s_memrealtime();
-  }
   for (int t = 0; t < n_tiles; ++t) {
     // tile t landed for this wave once only the (NS-2) younger tiles' pieces remain; the barrier
     // makes every wave's pieces visible and retires every wave's reads of slot (t-1) % NS
-    if constexpr (ABL != 1) wait_vmcnt<LOADS * (NS - 2)>();
+    wait_vmcnt<LOADS * (NS - 2)>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     const uint32_t tbase = lds_smem + (uint32_t)((t % NS) * TILE_BYTES);
     const int row0 = row_begin + t * TR;
     const int prow0 = phys_tile(row0 / TR) * TR;
     const int tnext = t + NS - 1;
-    auto dma = [&](int i) {
-      if constexpr (ABL != 1) issue_piece(tnext, i);
-    };
+    auto dma = [&](int i) { issue_piece(tnext, i); };
     const uint32_t fb = tbase + foff;   // this lane's fragment in piece 0 of sub-tile 0
-    if constexpr (ABL == 4) {
-#pragma unroll
-      for (int i = 0; i < LOADS; ++i) dma(i);
-      continue;
-    }
     mq_prologue<0>(a, fb + j0 * NKS * PIECE);
     // (this wave's sub-tiles are j0 .. j0 + NSW - 1; ``last`` = row offset of its last one)
     const int last = (j0 + NSW - 1) * SUB;
@@ -416,14 +397,6 @@ __global__ __launch_bounds__(512, 1) void index_scan_mq_kernel(
   }
   if (nst) flush();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tail prefetches and emissions
-  if constexpr (ABL == 3) {
-    const uint64_t cyc = __builtin_amdgcn_s_memtime() - c0;
-    const uint64_t rt = __builtin_amdgcn_s_memrealtime() - r0t;
-    if (tid == 0) {
-      cand_s[2 * blockIdx.x] = (float)cyc;
-      cand_s[2 * blockIdx.x + 1] = (float)rt;
-    }
-  }
 }
 
 // Wave-wide max of a float, valid in lane 63: DPP row shifts fold each 16-lane row, then two row
@@ -751,39 +724,18 @@ int symb_mq_max_sets(int dim) {
 }
 
 // rows_per_blk must be a multiple of 64; n_rblk * rows_per_blk >= n_valid.  cand_n is zeroed here.
-// cache policy of the row stream (symb_mq_config): 0 default, 2 non-temporal
-static int g_mq_aux = 0;
-int symb_mq_config(int aux) {
-  if (aux != 0 && aux != 2) return -1;
-  g_mq_aux = aux;
-  return 0;
-}
-
-template <int D, int NSET, int RSPLIT, int AUX>
-static int launch_mq_aux(const void* X, int n_valid, int rows_per_blk, int n_rblk, const void* Q,
+template <int D, int NSET, int RSPLIT>
+static int launch_mq(const void* X, int n_valid, int rows_per_blk, int n_rblk, const void* Q,
                      int NQ, const float* thr, float* cand_s, int* cand_i, int* cand_n, int cap,
                      int xcd, hipStream_t st, int tshift, const int* gate, MqList lst) {
   constexpr int qpb = mq::WAVES / RSPLIT * 16 * NSET;
   const int n_qblk = (NQ + qpb - 1) / qpb;
   constexpr int lds = MqGeo<D>::LDS_BYTES;
-  set_max_lds<index_scan_mq_kernel<D, NSET, 0, RSPLIT, AUX>>(lds);
-  hipLaunchKernelGGL((index_scan_mq_kernel<D, NSET, 0, RSPLIT, AUX>), dim3(n_rblk * n_qblk),
+  set_max_lds<index_scan_mq_kernel<D, NSET, RSPLIT>>(lds);
+  hipLaunchKernelGGL((index_scan_mq_kernel<D, NSET, RSPLIT>), dim3(n_rblk * n_qblk),
                      dim3(512), lds, st, (const __bf16*)X, n_valid, rows_per_blk, (const __bf16*)Q,
                      NQ, n_qblk, xcd, thr, cand_s, cand_i, cand_n, cap, tshift, gate, lst);
   return (int)hipGetLastError();
-}
-
-template <int D, int NSET, int RSPLIT>
-static int launch_mq(const void* X, int n_valid, int rows_per_blk, int n_rblk, const void* Q,
-                     int NQ, const float* thr, float* cand_s, int* cand_i, int* cand_n, int cap,
-                     int xcd, hipStream_t st, int tshift, const int* gate, MqList lst) {
-  return g_mq_aux == 2
-             ? launch_mq_aux<D, NSET, RSPLIT, 2>(X, n_valid, rows_per_blk, n_rblk, Q, NQ, thr,
-                                                 cand_s, cand_i, cand_n, cap, xcd, st, tshift,
-                                                 gate, lst)
-             : launch_mq_aux<D, NSET, RSPLIT, 0>(X, n_valid, rows_per_blk, n_rblk, Q, NQ, thr,
-                                                 cand_s, cand_i, cand_n, cap, xcd, st, tshift,
-                                                 gate, lst);
 }
 
 // dim: 384 (sets 4 or 2; rsplit 2 with sets 4), 768 (sets 2), 1024 (sets 1); rsplit 1 otherwise.
@@ -818,47 +770,6 @@ int symb_index_scan_mq(const void* X, int n_valid, int rows_per_blk, int n_rblk,
   if (rsplit == 2) return SYMB_MQ(384, 4, 2);
   return sets == 4 ? SYMB_MQ(384, 4, 1) : SYMB_MQ(384, 2, 1);
 #undef SYMB_MQ
-}
-
-// Profiling-only entry: the ablations of index_scan_mq_kernel (ABL above), D = 384, same arguments.
-int symb_index_scan_mq_ablate(const void* X, int n_valid, int rows_per_blk, int n_rblk,
-                              const void* Q, int NQ, const float* thr, float* cand_s, int* cand_i,
-                              int* cand_n, int cap, int xcd, hipStream_t st, int abl, int sets,
-                              int rsplit) {
-  if (NQ <= 0) return 0;
-  if (rows_per_blk % 64 || n_rblk <= 0 || thr == nullptr || cap <= 0) return -1;
-  if (sets != 2 && sets != 4) return -1;
-  if (rsplit != 1 && !(rsplit == 2 && sets == 4)) return -1;
-  hipError_t e = hipMemsetAsync(cand_n, 0, sizeof(int) * (size_t)NQ, st);
-  if (e != hipSuccess) return (int)e;
-  const int qpb = mq::WAVES / rsplit * 16 * sets;
-  const int n_qblk = (NQ + qpb - 1) / qpb;
-  constexpr int lds = MqGeo<384>::LDS_BYTES;
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL(kern, dim3(n_rblk * n_qblk), dim3(512), lds, st, (const __bf16*)X,
-                       n_valid, rows_per_blk, (const __bf16*)Q, NQ, n_qblk, xcd, thr, cand_s,
-                       cand_i, cand_n, cap, 0, (const int*)nullptr, MqList{nullptr, 0});
-    return (int)hipGetLastError();
-  };
-  switch (abl + 8 * (sets == 2) + 16 * (rsplit == 2)) {
-    case 0: return go(index_scan_mq_kernel<384, 4, 0>);
-    case 1: return go(index_scan_mq_kernel<384, 4, 1>);
-    case 2: return go(index_scan_mq_kernel<384, 4, 2>);
-    case 3: return go(index_scan_mq_kernel<384, 4, 3>);
-    case 4: return go(index_scan_mq_kernel<384, 4, 4>);
-    case 8: return go(index_scan_mq_kernel<384, 2, 0>);
-    case 9: return go(index_scan_mq_kernel<384, 2, 1>);
-    case 10: return go(index_scan_mq_kernel<384, 2, 2>);
-    case 11: return go(index_scan_mq_kernel<384, 2, 3>);
-    case 12: return go(index_scan_mq_kernel<384, 2, 4>);
-    case 16: return go(index_scan_mq_kernel<384, 4, 0, 2>);
-    case 17: return go(index_scan_mq_kernel<384, 4, 1, 2>);
-    case 18: return go(index_scan_mq_kernel<384, 4, 2, 2>);
-    case 19: return go(index_scan_mq_kernel<384, 4, 3, 2>);
-    case 20: return go(index_scan_mq_kernel<384, 4, 4, 2>);
-    default: return -1;
-  }
 }
 
 // ovf (one int) is zeroed here (reset_ovf), then set by any query whose buffer overflowed.

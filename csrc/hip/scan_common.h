@@ -149,4 +149,28 @@ __device__ __forceinline__ void frag_prologue(bf16x8 (&a)[R], const uint32_t (&v
   if constexpr (J + 1 < PF) frag_prologue<J + 1, PF, M, R>(a, voff, base);
 }
 
+// ---- pieces the register-list scans share ------------------------------------------------------
+// (bf16: index_scan_topk_kernel and its masked form index_scan_filter_kernel; acc_reg_row also
+// the masked fp8 scan.)  M32: 32x32 MFMA tiles (bf16 at D = 384, fp8), else 16x16.  Only what
+// leaves every instantiation's instruction stream as it was is shared: the other setup pieces are
+// textually equal within a pair, but as helpers each of them rescheduled the kernels' prologues
+// (profiles/retire_scan_diag/README.md has the list).
+
+// Row, within its sub-tile, of accumulator register r of a lane, less the lane's own
+// 4 * (lane >> 5) (32x32: four rows of every eight) or 4 * (lane >> 4) (16x16: four in a row).
+template <bool M32>
+__device__ __forceinline__ constexpr int acc_reg_row(int r) {
+  return M32 ? (r & 3) + 8 * (r >> 2) : r;
+}
+
+// The query's B fragments: k-step ks of a lane is 8 consecutive k of Q[query] (qp).
+template <int D, bool M32, int NKS>
+__device__ __forceinline__ void load_query_frags(bf16x8 (&qf)[NKS], const __bf16* qp, int lane) {
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) {
+    const int k0 = M32 ? ks * 16 + (lane >> 5) * 8 : ks * 32 + (lane >> 4) * 8;
+    qf[ks] = *reinterpret_cast<const bf16x8*>(qp + k0);
+  }
+}
+
 }  // namespace symb
