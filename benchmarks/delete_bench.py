@@ -1,0 +1,176 @@
+#!/usr/bin/env python3
+"""Search over a shard with tombstones (HbmIndexShard.delete_rows, csrc/hip/index_delete.hip): what
+a delete costs every later search under the two routes, on one shard of random unit rows with
+held-out random queries.
+
+    delete_route = "zero"   the unmasked route (pruned / list scan) + the dead-id check + the
+                            gated masked scan, which exits at once while no dead row came back
+    delete_route = "mask"   every search with tombstones is the masked list scan under ~dead
+
+First the search before any delete, in two alternated runs of the same call (``search_a`` /
+``search_b``): the spread between them is what the no-delete search shows by itself.  Then, after
+each cumulative delete level (shares of the rows, as uniform random rows or as runs of 200 rows,
+"documents"), in alternated rounds on the same shard, one JSON line per variant:
+
+  route_only   shard._search_route(q, k): the search code as it runs before any delete, over the
+               same bytes (zeroed rows included) -- the yardstick of the "zero" route's overhead
+  zero         shard.search(q, k) under delete_route = "zero"
+  mask         shard.search(q, k) under delete_route = "mask"
+
+Every line carries ``last_dead_hits`` (must be 0: each query keeps k live rows scoring above 0),
+``rows_equal_mask`` (the result against the masked scan's: same rows outside runs of equal scores)
+and ``max_abs_vs_mask``; the ``delete`` lines carry the cost of the delete itself per 1k rows.
+
+    python benchmarks/delete_bench.py [--rows 100000000] [--dim 384] [--dtype bf16|fp8]
+        [--prune i8|none] [--pattern uniform|docs] [--levels 0.01,1,10] [--nq 256] [--k 10]
+        [--rounds 3] [--iters 5] [--out FILE]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+DOC_ROWS = 200
+
+
+def pick_rows(pattern: str, n: int, n_new: int, live: torch.Tensor, g) -> torch.Tensor:
+    """~n_new live rows to delete: uniform random rows, or whole runs of DOC_ROWS rows."""
+    dev = live.device
+    if pattern == "uniform":
+        hit = (torch.rand(n, device=dev, generator=g) < n_new / max(1, int(live.sum()))) & live
+        return torch.nonzero(hit).flatten()
+    n_docs = max(1, round(n_new / DOC_ROWS))
+    starts = torch.randint(0, n - DOC_ROWS, (n_docs,), device=dev, generator=g)
+    edge = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    one = torch.ones(n_docs, dtype=torch.int32, device=dev)
+    edge.index_add_(0, starts, one)
+    edge.index_add_(0, starts + DOC_ROWS, -one)
+    return torch.nonzero((torch.cumsum(edge[:n], 0, dtype=torch.int32) > 0) & live).flatten()
+
+
+def rows_equal_outside_ties(s, r, ref_s, ref_r, tol: float) -> bool:
+    tie = torch.zeros_like(r, dtype=torch.bool)
+    for a in (s, ref_s):
+        tie[:, 1:] |= (a[:, 1:] - a[:, :-1]).abs() <= tol
+        tie[:, :-1] |= (a[:, :-1] - a[:, 1:]).abs() <= tol
+    return bool(((r == ref_r) | tie).all())
+
+
+def timed(fn, iters: int) -> float:
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e3
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=100_000_000)
+    ap.add_argument("--dim", type=int, default=384)
+    ap.add_argument("--dtype", choices=("bf16", "fp8"), default="bf16")
+    ap.add_argument("--prune", default="i8", help="i8 (bf16 shards) or none")
+    ap.add_argument("--pattern", choices=("uniform", "docs"), default="uniform")
+    ap.add_argument("--levels", default="0.01,1,10", help="cumulative dead shares, percent")
+    ap.add_argument("--nq", type=int, default=256)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("delete_bench needs the GPU: nothing here is measured without one")
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    dev = torch.device("cuda")
+    n, k = a.rows, a.k
+    prune = "i8" if (a.prune == "i8" and a.dtype == "bf16") else None
+    shard = HbmIndexShard(a.dim, n, device=dev, dtype=a.dtype, prune=prune)
+    shard.fill_random(n, seed=1)
+    g = torch.Generator(device=dev).manual_seed(77)      # held out: not rows of the shard
+    q = torch.nn.functional.normalize(torch.randn(a.nq, a.dim, device=dev, generator=g),
+                                      dim=-1).bfloat16()
+    out = open(a.out, "a") if a.out else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+    base = {"bench": "delete_bench", "rows": n, "dim": a.dim, "dtype": a.dtype,
+            "prune": prune or "none", "pattern": a.pattern, "nq": a.nq, "k": k,
+            "rounds": a.rounds, "iters": a.iters}
+    tol = 2e-3
+
+    def run(variants: dict, info: dict, ref=None) -> dict:
+        """Alternated rounds of every variant; one line each; returns (medians, all times)."""
+        res, hits = {}, {}
+        for v, fn in variants.items():               # results first (also the warm-up)
+            shard.last_dead_hits = None
+            res[v] = fn()
+            hits[v] = 0 if shard.last_dead_hits is None else int(shard.last_dead_hits)
+        torch.cuda.synchronize()
+        times = {v: [] for v in variants}
+        for _ in range(a.rounds):
+            for v, fn in variants.items():
+                times[v].append(timed(fn, a.iters))
+        med = {}
+        for v, ts in times.items():
+            extra = {}
+            if ref is not None:
+                s, r = res[v]
+                extra = {"rows_equal_mask": rows_equal_outside_ties(s, r, ref[0], ref[1], tol),
+                         "max_abs_vs_mask": float((s - ref[0]).abs().max())}
+            med[v] = statistics.median(ts)
+            emit(dict(info, variant=v, ms=round(med[v], 3), ms_min=round(min(ts), 3),
+                      ms_max=round(max(ts), 3), last_dead_hits=hits[v], **extra))
+        return med, times
+
+    def search(route):
+        shard.delete_route = route
+        return shard.search(q, k)
+
+    # before any delete: the same call in two alternated runs
+    plain, pt = run({"search_a": lambda: shard.search(q, k),
+                     "search_b": lambda: shard.search(q, k)}, dict(base, dead=0, dead_share=0.0))
+    # (the range of every round of both runs)
+    spread = max(pt["search_a"] + pt["search_b"]) - min(pt["search_a"] + pt["search_b"])
+    live = torch.ones(n, dtype=torch.bool, device=dev)
+    for li, level in enumerate(float(x) for x in a.levels.split(",")):
+        want = round(level / 100.0 * n) - shard.n_dead
+        rows = pick_rows(a.pattern, n, want, live, g)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n_new = shard.delete_rows(rows)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) * 1e3
+        live[rows] = False
+        del rows
+        info = dict(base, dead=shard.n_dead, dead_share=round(shard.n_dead / n, 6))
+        emit(dict(info, variant="delete", deleted=n_new, ms=round(dt, 3),
+                  ms_per_1k_rows=round(dt / max(1, n_new) * 1e3, 4)))
+        ref = search("mask")
+        torch.cuda.synchronize()
+        med, _ = run({"route_only": lambda: shard._search_route(q, k, None),
+                      "zero": lambda: search("zero"), "mask": lambda: search("mask")}, info, ref)
+        over = med["zero"] - med["route_only"]
+        emit(dict(info, variant="summary", no_delete_ms=round(plain["search_a"], 3),
+                  no_delete_spread_ms=round(spread, 3), zero_overhead_ms=round(over, 3),
+                  zero_overhead_within_spread=bool(over <= spread),
+                  zero_vs_no_delete_ms=round(med["zero"] - plain["search_a"], 3),
+                  zero_beats_mask=bool(med["zero"] < med["mask"])))
+
+
+if __name__ == "__main__":
+    main()

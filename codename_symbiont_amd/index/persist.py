@@ -6,12 +6,15 @@ The HBM index is volatile, so each shard directory holds a log-structured snapsh
 
   CURRENT                   commit pointer: "manifest.<gen>.json" (atomic replace + fsync)
   manifest.<gen>.json       {"format": 2, gen, dim, dtype, count, segments, patches, payloads}
+                            (+ "dead": {gen, n} once the shard holds tombstones)
   seg.<gen>.npy             rows [row0, row0 + n) as captured at generation gen (bf16 bit patterns
                             as uint16, or e4m3 bytes; .npy, memory-mappable)
   patch.<gen>.rows.npy      overwritten rows (int64 row ids) of OLDER segments ...
   patch.<gen>.vecs.npy      ... and their contents at generation gen
   pay.<gen>.bin             payload delta: the rows whose point id / payload changed since the
                             previous generation (columnar binary, see write_payloads)
+  dead.<gen>.bin            the tombstone bitmap of rows [0, count) (bit r % 8 of byte r // 8),
+                            written whole by a cut after which it changed
   wal.log, wal.<seq>.log    the live WAL and WAL files rotated out at a snapshot cut
 
 A snapshot writes only what changed since the previous one -- the new rows (one segment), the
@@ -36,7 +39,8 @@ committed manifest -> HBM, then replay of the uncovered WAL files in order.
 
 WAL record: magic u32 | n u32 | body_len u32 | crc32(body) u32 | body, body = n x
 (u16 id_len, id, u32 payload_len, payload JSON, f32[dim]).  A torn tail record (crash mid-write)
-fails its length/CRC check and is dropped on replay.
+fails its length/CRC check and is dropped on replay.  A delete record has the same header under
+a second magic ("SYMD") and the body n x (u16 id_len, id); replay applies both kinds in file order.
 
 Directories written by the previous full-rewrite format (``snapshot.<gen>/`` with vectors.npy +
 payloads.jsonl, CURRENT naming it, or the older ``snapshot/``) still load.
@@ -56,7 +60,8 @@ from .shard import HbmIndexShard, Payload
 
 log = logging.getLogger("symbiont.index")
 
-MAGIC = 0x53594D42  # "SYMB"
+MAGIC = 0x53594D42  # "SYMB": an upsert record
+MAGIC_DELETE = 0x53594D44  # "SYMD": a delete record
 _HDR = struct.Struct("<IIII")
 
 
@@ -82,6 +87,16 @@ class Wal:
             parts += [struct.pack("<H", len(b)), b, struct.pack("<I", len(pj)), pj, v.tobytes()]
         body = b"".join(parts)
         self._f.write(_HDR.pack(MAGIC, len(point_ids), len(body), zlib.crc32(body)) + body)
+        self._f.flush()
+        os.fsync(self._f.fileno())
+
+    def append_delete(self, point_ids: list[str]) -> None:
+        parts = []
+        for pid in point_ids:
+            b = pid.encode()
+            parts += [struct.pack("<H", len(b)), b]
+        body = b"".join(parts)
+        self._f.write(_HDR.pack(MAGIC_DELETE, len(point_ids), len(body), zlib.crc32(body)) + body)
         self._f.flush()
         os.fsync(self._f.fileno())
 
@@ -115,7 +130,8 @@ class Wal:
         while off + _HDR.size <= len(data):
             magic, _n, blen, crc = _HDR.unpack_from(data, off)
             body = data[off + _HDR.size: off + _HDR.size + blen]
-            if magic != MAGIC or len(body) != blen or zlib.crc32(body) != crc:
+            if (magic not in (MAGIC, MAGIC_DELETE) or len(body) != blen
+                    or zlib.crc32(body) != crc):
                 break
             off += _HDR.size + blen
         if off != len(data):
@@ -127,7 +143,16 @@ class Wal:
 
     @staticmethod
     def replay(path: str, dim: int):
-        """Yields (point_ids, payloads, vecs) per intact record."""
+        """Yields (point_ids, payloads, vecs) per intact upsert record (deletes are skipped:
+        ``replay_ops`` has both)."""
+        for op in Wal.replay_ops(path, dim):
+            if op[0] == "upsert":
+                yield op[1], op[2], op[3]
+
+    @staticmethod
+    def replay_ops(path: str, dim: int):
+        """Yields ("upsert", point_ids, payloads, vecs) and ("delete", point_ids) per intact
+        record, in file order."""
         if not os.path.exists(path):
             return
         with open(path, "rb") as f:
@@ -136,11 +161,20 @@ class Wal:
         while off + _HDR.size <= len(data):
             magic, n, blen, crc = _HDR.unpack_from(data, off)
             body = data[off + _HDR.size: off + _HDR.size + blen]
-            if magic != MAGIC or len(body) != blen or zlib.crc32(body) != crc:
+            if (magic not in (MAGIC, MAGIC_DELETE) or len(body) != blen
+                    or zlib.crc32(body) != crc):
                 break  # torn / corrupt tail
             off += _HDR.size + blen
             ids, pls, vs = [], [], []
             o = 0
+            if magic == MAGIC_DELETE:
+                for _ in range(n):
+                    (lb,) = struct.unpack_from("<H", body, o)
+                    o += 2
+                    ids.append(body[o:o + lb].decode())
+                    o += lb
+                yield "delete", ids
+                continue
             for _ in range(n):
                 (lb,) = struct.unpack_from("<H", body, o)
                 o += 2
@@ -153,7 +187,7 @@ class Wal:
                 pls.append(Payload(*a))
                 vs.append(np.frombuffer(body, dtype=np.float32, count=dim, offset=o))
                 o += 4 * dim
-            yield ids, pls, np.stack(vs) if vs else np.zeros((0, dim), np.float32)
+            yield "upsert", ids, pls, np.stack(vs) if vs else np.zeros((0, dim), np.float32)
 
 
 def wal_files(directory: str, after_gen: int) -> list[str]:
@@ -412,8 +446,9 @@ class SnapshotJob:
     stream from the older files, or a segment file the cut already wrote (``seg_file``)."""
 
     def __init__(self, directory: str, gen: int, manifest: dict, seg, patch, pay, pay_merge,
-                 cleanup_wal_upto: int | None):
+                 cleanup_wal_upto: int | None, dead: bytes | None = None):
         self.directory, self.gen, self.manifest = directory, gen, manifest
+        self.dead = dead     # the tombstone bitmap captured at the cut, when it changed
         self.seg, self.patch, self.pay, self.pay_merge = seg, patch, pay, pay_merge
         self.cleanup_wal_upto = cleanup_wal_upto
         self.bytes_written = 0
@@ -446,6 +481,12 @@ class SnapshotJob:
             else:
                 os.replace(tmp, os.path.join(d, f"pay.{g}.bin"))
             self.bytes_written += os.path.getsize(os.path.join(d, f"pay.{g}.bin"))
+        if self.dead is not None:
+            with open(os.path.join(d, f"dead.{g}.bin"), "wb") as f:
+                f.write(self.dead)
+                f.flush()
+                os.fsync(f.fileno())
+            self.bytes_written += len(self.dead)
         man = os.path.join(d, f"manifest.{g}.json")
         write_atomic(man, json.dumps(self.manifest).encode())
         if _crash_before_commit:
@@ -461,6 +502,8 @@ class SnapshotJob:
         keep |= {f"seg.{s['gen']}.npy" for s in m["segments"]}
         keep |= {f"patch.{p['gen']}.{x}.npy" for p in m["patches"] for x in ("rows", "vecs")}
         keep |= {f"pay.{p['gen']}.bin" for p in m["payloads"]}
+        if m.get("dead"):
+            keep.add(f"dead.{m['dead']['gen']}.bin")
         for fn in os.listdir(d):
             path = os.path.join(d, fn)
             if fn in keep:
@@ -474,7 +517,8 @@ class SnapshotJob:
                 if self.cleanup_wal_upto is not None and int(parts[1]) <= self.cleanup_wal_upto:
                     os.remove(path)
                 continue
-            if parts[0] in ("seg", "patch", "pay", "manifest") and len(parts) >= 3 and parts[1].isdigit():
+            if (parts[0] in ("seg", "patch", "pay", "dead", "manifest") and len(parts) >= 3
+                    and parts[1].isdigit()):
                 os.remove(path)
         fsync_dir(d)
 
@@ -538,7 +582,7 @@ class ShardPersister:
         for fn in os.listdir(self.directory):
             parts = fn.split(".")
             if len(parts) >= 2 and parts[1].isdigit() and parts[0] in (
-                    "seg", "patch", "pay", "manifest", "wal", "snapshot"):
+                    "seg", "patch", "pay", "dead", "manifest", "wal", "snapshot"):
                 g = max(g, int(parts[1]))
         return g + 1
 
@@ -620,6 +664,15 @@ class ShardPersister:
             pays.append({"gen": gen, "m": m_new})
         manifest = {"format": 2, "gen": gen, "dim": shard.dim, "dtype": shard.dtype, "count": n,
                     "segments": segs, "patches": patches, "payloads": pays}
+        # tombstones: the whole bitmap of rows [0, n) when it changed since the last cut, else
+        # the previous file carried forward
+        dead = None
+        if shard.n_dead:
+            if incremental and man.get("dead") and shard._dead_cut_gen == shard.dead_gen:
+                manifest["dead"] = dict(man["dead"])
+            else:
+                dead = shard._dead_host[:(n + 7) // 8].tobytes()
+                manifest["dead"] = {"gen": gen, "n": shard.n_dead}
         if rotate_wal is not None:
             rotate_wal(gen)
         # the shard's change record now starts from this cut
@@ -628,8 +681,9 @@ class ShardPersister:
         shard._dirty = set()
         ps.dirty = set()
         shard._persist_key = (os.path.abspath(d), gen)
+        shard._dead_cut_gen = shard.dead_gen
         return SnapshotJob(d, gen, manifest, seg, patch, pay, merge,
-                           cleanup_wal_upto=gen if rotate_wal is not None else None)
+                           cleanup_wal_upto=gen if rotate_wal is not None else None, dead=dead)
 
     def load(self, shard: HbmIndexShard) -> int:
         man = committed_manifest(self.directory)
@@ -663,6 +717,14 @@ class ShardPersister:
             for r, (pid, f) in zip(keys.tolist(), ents):
                 if r < n:
                     shard.payloads.set(r, pid, None if f is None else Payload(*f))
+        if man.get("dead"):
+            # through delete_rows: the rows are zero (with their images) even if the patch that
+            # zeroed them were missing, and the bitmap, n_dead and the payload store agree
+            with open(os.path.join(d, f"dead.{man['dead']['gen']}.bin"), "rb") as f:
+                bits = np.frombuffer(f.read(), np.uint8)
+            rows = np.flatnonzero(np.unpackbits(bits, bitorder="little")[:n])
+            shard.delete_rows(rows.tolist())
+            shard._dead_cut_gen = shard.dead_gen
         shard.payloads.dirty = set()
         shard.payloads.track = True
         shard.publish()

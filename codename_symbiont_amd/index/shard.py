@@ -19,6 +19,7 @@ import os
 import threading
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 TILE_ROWS = 64  # scan tile: 2 MFMA sub-tiles per barrier interval
@@ -127,6 +128,11 @@ class PayloadStore:
         if self.track:
             self.dirty.add(row)
 
+    def remove(self, row: int) -> None:
+        """Forget the row's point id, payload and value-index entries (a deleted point); the row
+        is marked dirty, so the next snapshot's payload delta records it as empty."""
+        self.set(row, None, None)
+
     def get(self, row: int) -> tuple[str | None, Payload]:
         t = self.fields.get(row)
         if t is None:
@@ -208,6 +214,9 @@ def _pack_bits(allow: torch.Tensor, n_words: int) -> torch.Tensor:
     return (pad.view(-1, 8) * w).sum(1, dtype=torch.uint8)
 
 
+_POPCOUNT8 = np.array([bin(i).count("1") for i in range(256)], dtype=np.int64)
+
+
 def _unpack_bits(packed: torch.Tensor) -> torch.Tensor:
     """uint8 [m] -> bool [8 m] (the inverse of _pack_bits)."""
     sh = torch.arange(8, dtype=torch.uint8, device=packed.device)
@@ -222,12 +231,16 @@ class RowMask:
     whole 64-bit words; bits at or past ``visible`` are clear.  ``visible``: the shard's visible
     rows when the mask was built -- rows appended later are disallowed under it.  ``tiles`` /
     ``n_live`` (shards the masked scan serves, else None): the ascending 64-row tiles that hold
-    an allowed row and their count, device tensors from ``filter_tiles``."""
+    an allowed row and their count, device tensors from ``filter_tiles``.  ``dead_gen``: the
+    shard's delete generation when the mask was built (tombstoned rows are cleared in it); a
+    search refuses a mask from before a later delete, which could return a deleted row."""
 
-    __slots__ = ("bits", "visible", "tiles", "n_live")
+    __slots__ = ("bits", "visible", "tiles", "n_live", "dead_gen")
 
-    def __init__(self, bits: torch.Tensor, visible: int, tiles=None, n_live=None):
+    def __init__(self, bits: torch.Tensor, visible: int, tiles=None, n_live=None,
+                 dead_gen: int = 0):
         self.bits, self.visible, self.tiles, self.n_live = bits, int(visible), tiles, n_live
+        self.dead_gen = int(dead_gen)
 
     @property
     def words(self) -> torch.Tensor:
@@ -397,6 +410,23 @@ class HbmIndexShard:
         self._persisted = 0
         self._dirty: set[int] = set()
         self._persist_key = None
+        # tombstones (delete_rows): the device bitmap of deleted rows (uint8, whole 64-bit words
+        # over the slab, packed as a RowMask: bit r % 64 of word r // 64), allocated by the first
+        # delete so a shard that never deletes pays nothing; its host copy (what persistence
+        # writes); the dead rows below ``count``; and the delete generation, bumped by every
+        # delete (RowMasks carry it, the live mask and the snapshot cut compare it)
+        self.dead = None
+        self._dead_host = None
+        self.n_dead = 0
+        self.dead_gen = 0
+        self._dead_cut_gen = 0       # dead_gen the last snapshot cut / load saw
+        # how a search treats tombstones: "zero" = the unmasked route + the dead-id check + the
+        # gated masked scan (_search_tombstoned), "mask" = always the masked scan
+        self.delete_route = self.DELETE_ROUTE_DEFAULT[dtype]
+        self.last_dead_hits = None   # device int32 [1]: dead ids the last search's route returned
+        self._live_mask = None
+        self._live_key = None
+        self._zero_hits = None
 
     # ------------------------------------------------------------------ pruning images
     def _stream_rec(self, form: int) -> int:
@@ -568,6 +598,17 @@ class HbmIndexShard:
         self.visible = min(self.visible, n)
         self._persisted = min(self._persisted, n)
         self._dirty = {r for r in self._dirty if r < n}
+        if self.n_dead:
+            # the forgotten slots are written anew by later appends: their tombstones go
+            h = self._dead_host
+            h[(n + 7) // 8:] = 0
+            if n % 8:
+                h[n // 8] &= (1 << (n % 8)) - 1
+            self.dead.copy_(torch.from_numpy(h))
+            left = int(_POPCOUNT8[h].sum())
+            if left != self.n_dead:
+                self.n_dead = left
+                self.dead_gen += 1
 
     def _mark_written(self, rows) -> None:
         """Rows overwritten in place: remember the ones the last snapshot already covers."""
@@ -941,6 +982,99 @@ class HbmIndexShard:
         self.publish()
         return [row_of[pid] for pid in point_ids]
 
+    # ------------------------------------------------------------------ deletes (tombstones)
+    # ``delete_route`` a new shard starts with, per row format (profiles/r10_delete/ has the A/B,
+    # 100M rows, 256 held-out queries).  bf16: "zero" keeps the pruned search at its own speed,
+    # 10.9 ms against 18-21 ms for the masked scan.  fp8: both routes are the same seeded list
+    # scan; "zero" is 0.1-0.8 ms ahead after uniform deletes, but after deletes by document
+    # (runs of rows, what VectorStore.delete(filter=) produces) the masked scan skips the dead
+    # tiles and is 1.1 ms (4.6 %) ahead at 10 % dead, so there the default is "mask"
+    DELETE_ROUTE_DEFAULT = {"bf16": "zero", "fp8": "mask"}
+
+    @property
+    def live_count(self) -> int:
+        """Rows that are not tombstoned (``count`` stays the physical row count)."""
+        return self.count - self.n_dead
+
+    def delete_rows(self, rows) -> int:
+        """Tombstone rows; returns how many were newly deleted (duplicates and rows already
+        dead are ignored, a row outside [0, count) raises IndexError).
+
+        A deleted row is zeroed everywhere -- the bf16 / e4m3 row, the prefilter image, and the
+        pruning images, re-imaged from the zero row -- and its bit is set in ``dead``.  A zero
+        row scores exactly 0 in every scan and image (the quantisers guard amax > 0) and the
+        tracked bounds only grow, so every unmasked route stays exact over the PHYSICAL rows;
+        ``search`` then checks the returned ids against ``dead`` (_search_tombstoned).  The row's
+        point id and payload go; the slot is never reused and capacity is not reclaimed."""
+        if isinstance(rows, torch.Tensor):
+            rows = rows.flatten().cpu().numpy()
+        elif not isinstance(rows, np.ndarray):
+            rows = list(rows)
+        ra = np.unique(np.asarray(rows, dtype=np.int64))      # sorted, distinct
+        if ra.size and (ra[0] < 0 or ra[-1] >= self.count):
+            raise IndexError(f"delete_rows: row outside the shard's {self.count} rows")
+        if self._dead_host is not None:
+            ra = ra[(self._dead_host[ra >> 3] >> (ra & 7).astype(np.uint8)) & 1 == 0]
+        if not ra.size:
+            return 0
+        if self.dead is None:
+            nbytes = self.rows.shape[0] // 8     # (the slab is whole 64-row tiles)
+            self.dead = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+            self._dead_host = np.zeros(nbytes, dtype=np.uint8)
+        h = self._dead_host
+        np.bitwise_or.at(h, ra >> 3, (1 << (ra & 7)).astype(np.uint8))
+        if self.payloads.track and self._persisted:
+            # a snapshot patches the zeros over the rows it covers
+            self._mark_written(ra[ra < self._persisted].tolist())
+        idx = torch.from_numpy(ra.astype(np.int32)).to(self.device)
+        if self.device.type == "cuda":
+            from ..ops import kernels as K
+
+            K.tombstone_rows(idx, self.count, self.dead.view(torch.int64), self.rows, self.rows8)
+        else:
+            self.rows.index_fill_(0, idx.long(), 0)
+            if self.rows8 is not None:
+                self.rows8.index_fill_(0, idx.long(), 0)
+            self.dead.copy_(torch.from_numpy(h))
+        if self.prune_on or self.mx4_on:
+            self._image_rows(rows=idx)
+        # (the payload store is sparse: walk whichever of the two is shorter)
+        ps = self.payloads
+        if len(ps.point_ids) + len(ps.fields) < ra.size:
+            gone = {r for d in (ps.point_ids, ps.fields) for r in d if (h[r >> 3] >> (r & 7)) & 1}
+        else:
+            gone = [r for r in ra.tolist() if r in ps.point_ids or r in ps.fields]
+        for r in gone:
+            ps.remove(r)
+        self.n_dead += int(ra.size)
+        self.dead_gen += 1
+        return int(ra.size)
+
+    def delete_points(self, point_ids) -> int:
+        """Delete the points with these ids; unknown ids are ignored (as Qdrant does).  Returns
+        the number of points deleted.  A later upsert of a deleted id appends a new row."""
+        id_to_row = self.payloads.id_to_row
+        return self.delete_rows([id_to_row[p] for p in point_ids if p in id_to_row])
+
+    def _live(self) -> RowMask:
+        """The RowMask of the rows that are not tombstoned: ~dead over the packed words (no bool
+        per row), with its tile list; rebuilt when a delete or the visible rows changed."""
+        key = (self.dead_gen, self.visible)
+        if self._live_mask is None or self._live_key != key:
+            v = self.visible
+            nw = max(1, (v + TILE_ROWS - 1) // TILE_ROWS)
+            words = ~self.dead.view(torch.int64)[:nw]
+            if v < nw * 64:      # bits at or past ``visible`` are clear in a RowMask
+                words[v // 64:v // 64 + 1].bitwise_and_((1 << (v % 64)) - 1)
+            tiles = n_live = None
+            if self.device.type == "cuda" and self._filter_scan_serves():
+                from ..ops.kernels import filter_tiles
+
+                tiles, n_live = filter_tiles(words, v)
+            self._live_mask = RowMask(words.view(torch.uint8), v, tiles, n_live, self.dead_gen)
+            self._live_key = key
+        return self._live_mask
+
     def fill_random(self, n: int, seed: int = 0, chunk: int = 1 << 20) -> None:
         """Synthetic unit rows straight into HBM (benchmark corpus; no payloads)."""
         g = torch.Generator(device=self.device)
@@ -959,9 +1093,17 @@ class HbmIndexShard:
         ``allow`` (a ``RowMask``, or anything ``make_mask`` takes): only those rows may be
         returned; the search is exact over them (_search_masked).
 
+        Tombstoned rows (``delete_rows``) are never returned (_search_tombstoned).
+
         Returns (scores f32 [NQ, k], rows int32 [NQ, k]); missing slots are (-inf, -1)."""
         if allow is not None:
             return self._search_masked(q_unit, k, n_cus, allow)
+        if self.n_dead == 0:
+            return self._search_route(q_unit, k, n_cus)
+        return self._search_tombstoned(q_unit, k, n_cus)
+
+    def _search_route(self, q_unit: torch.Tensor, k: int, n_cus):
+        """The unmasked search, exact over every physical row (zeroed tombstones included)."""
         NQ = q_unit.shape[0]
         k = int(k)
         if NQ == 0 or k <= 0:
@@ -989,6 +1131,52 @@ class HbmIndexShard:
             out_s.mul_(1.0 / (FP8_SCALE * FP8_SCALE))
         return out_s, out_i
 
+    def _zero_route_serves(self, NQ: int, k: int) -> bool:
+        """A search over tombstones runs the unmasked route plus the gated masked scan (else:
+        the masked scan or the masked matmul, directly)."""
+        return (self.delete_route == "zero" and self.device.type == "cuda" and 0 < k <= 32
+                and NQ > 0 and self._filter_scan_serves())
+
+    def _search_tombstoned(self, q_unit: torch.Tensor, k: int, n_cus):
+        """``search`` on a shard with tombstones, exact over the live rows, no host sync.
+
+        Every unmasked route is exact over the physical rows, and a dead row is a zero row there
+        (delete_rows).  If the top-k over that superset holds no dead row it IS the top-k over
+        the live rows, so: run the route unchanged, count the returned ids that are dead into a
+        device flag (results_dead), and enqueue the exact masked list scan under the live mask
+        gated on that flag -- with no hit its launches exit at once -- then take
+        where(hit, fallback, route).  No hit is the only outcome while every query has at least
+        k live rows scoring above 0, so each route keeps its own speed after deletes.
+        ``delete_route = "mask"`` goes straight to the masked scan; CPU shards, k > 32 and widths
+        the masked scan does not serve take the masked matmul."""
+        NQ, k = q_unit.shape[0], int(k)
+        if NQ == 0 or k <= 0:
+            return self._search_route(q_unit, k, n_cus)
+        live = self._live()
+        if self.device.type != "cuda" or k > 32 or not self._filter_scan_serves():
+            self.last_dead_hits = None
+            return self._search_matmul(q_unit, k, mask=live)
+        q = q_unit.to(torch.bfloat16).contiguous()
+        if self.delete_route != "zero":
+            if self._zero_hits is None:
+                self._zero_hits = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.last_dead_hits = self._zero_hits
+            return self._search_filtered(q, k, live, n_cus)
+        out_s, out_i = self._search_route(q, k, n_cus)
+        return self._dead_fallback(q, k, n_cus, live, out_s, out_i)
+
+    def _dead_fallback(self, q, k: int, n_cus, live: RowMask, out_s, out_i):
+        """The dead-id check of a route's result and the gated exact fallback (its own
+        buffers: garbage while the flag is 0, never selected then)."""
+        from ..ops import kernels as K
+
+        hit = torch.zeros(1, dtype=torch.int32, device=self.device)
+        K.results_dead(out_i.contiguous(), self.dead.view(torch.int64), hit)
+        fb_s, fb_i = self._search_filtered(q, k, live, n_cus, gate=hit)
+        self.last_dead_hits = hit
+        take = hit > 0
+        return torch.where(take, fb_s, out_s), torch.where(take, fb_i, out_i)
+
     def search_begin(self, q_unit: torch.Tensor, k: int, n_cus: int | None = None, *,
                      allow=None) -> dict:
         """First half of ``search`` for a pipelined caller: on the pruned path, the query-side
@@ -1000,10 +1188,15 @@ class HbmIndexShard:
             return {"full": self.search(q_unit, k, n_cus, allow=allow)}
         q = q_unit.to(torch.bfloat16).contiguous()
         k = int(k)
+        tomb = self.n_dead > 0
+        if tomb and not self._zero_route_serves(q.shape[0], k):
+            return {"full": self.search(q_unit, k, n_cus)}
         if (self.device.type == "cuda" and self.prune and not self.prefilter and 0 < k <= 16
                 and q.shape[0] >= self.prune_min_nq and self._seed_rows(self.visible, k)):
             ctx = self._pruned_begin(q, k, n_cus)
             if ctx is not None:
+                if tomb:   # search_end checks the result against the live mask of THIS begin
+                    ctx["live"] = self._live()
                 return ctx
         return {"full": self.search(q, k, n_cus)}
 
@@ -1011,7 +1204,11 @@ class HbmIndexShard:
         """-> (scores f32 [NQ, k], rows int32 [NQ, k]) of a ``search_begin`` context."""
         if "full" in ctx:
             return ctx["full"]
-        return self._pruned_end(ctx)
+        out_s, out_i = self._pruned_end(ctx)
+        live = ctx.get("live")
+        if live is None:
+            return out_s, out_i
+        return self._dead_fallback(ctx["q"], ctx["k"], ctx["n_cus"], live, out_s, out_i)
 
     # ------------------------------------------------------------------ search under a row mask
     # seed pass of the masked scan on by default?  (profiles/r8_filter/ has the A/B)
@@ -1057,13 +1254,16 @@ class HbmIndexShard:
             ok = hit[:v]
         else:
             raise TypeError(f"make_mask: bool mask, int rows or packed uint8 bits, got {a.dtype}")
-        bits = _pack_bits(ok, max(1, (v + TILE_ROWS - 1) // TILE_ROWS))
+        nw = max(1, (v + TILE_ROWS - 1) // TILE_ROWS)
+        bits = _pack_bits(ok, nw)
+        if self.n_dead:      # a tombstoned row passes no mask
+            bits = (bits.view(torch.int64) & ~self.dead.view(torch.int64)[:nw]).view(torch.uint8)
         tiles = n_live = None
         if dev.type == "cuda" and self._filter_scan_serves():
             from ..ops.kernels import filter_tiles
 
             tiles, n_live = filter_tiles(bits.view(torch.int64), v)
-        return RowMask(bits, v, tiles, n_live)
+        return RowMask(bits, v, tiles, n_live, self.dead_gen)
 
     def _filter_scan_serves(self) -> bool:
         """A masked list scan exists for this shard's row format and width."""
@@ -1086,19 +1286,24 @@ class HbmIndexShard:
         mask = self.make_mask(allow)
         if mask.bits.device != self.device:
             raise ValueError(f"RowMask on {mask.bits.device}, shard on {self.device}")
+        if mask.dead_gen != self.dead_gen:
+            raise ValueError("RowMask made before a delete (it may allow a deleted row): make "
+                             "it again with make_mask")
         if (self.device.type == "cuda" and self._filter_scan_serves() and k <= 32
                 and mask.tiles is not None):
             return self._search_filtered(q_unit.to(torch.bfloat16).contiguous(), k, mask, n_cus)
         return self._search_matmul(q_unit, k, mask=mask)
 
-    def _search_filtered(self, q_unit, k: int, mask: RowMask, n_cus):
+    def _search_filtered(self, q_unit, k: int, mask: RowMask, n_cus, gate=None):
         """The masked list scan (index_filter.hip; index_filter_fp8.hip on an fp8 shard, whose
         queries are quantised to e4m3 here and whose raw scores, S^2 * cosine, are rescaled once
         at the end) + merge.  The grid and the candidate workspace are sized as if every tile
         were live; the kernel reads the live count on the device.  ``filter_seed``: a first pass
         over every FILTER_SEED_STRIDE-th live tile of each workgroup's slice sees allowed rows
         only, so its k-th best is a lower bound on the final k-th allowed score (-inf where it
-        found fewer than k rows); the full pass starts from it.  Exact either way."""
+        found fewer than k rows); the full pass starts from it.  Exact either way.  ``gate`` (int32
+        device flag): every scan and merge launch runs only if it is non-zero (the outputs are
+        then left unwritten; the torch glue between the passes runs on whatever they hold)."""
         from ..ops import kernels as K
         from ..ops._ext import hip, stream_handle
 
@@ -1128,9 +1333,9 @@ class HbmIndexShard:
 
         def one_pass(thr, stride):
             scan(self.rows, n, mask.words, mask.tiles, mask.n_live, q_unit, kmax, n_rblk, cs, ci,
-                 thr, stride, self.scan_xcd)
+                 thr, stride, self.scan_xcd, gate)
             h.topk_merge(cs.data_ptr(), ci.data_ptr(), NQ, ncand, kmax, k, out_s.data_ptr(),
-                         out_i.data_ptr(), 0, 0, st, 0)
+                         out_i.data_ptr(), 0, 0, st, 0 if gate is None else gate.data_ptr())
 
         thr = None
         if self.filter_seed:

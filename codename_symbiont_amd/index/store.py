@@ -121,9 +121,12 @@ class VectorStore:
             # cut and its commit leaves the rotated file of that cut)
             for path in wal_files(snapshot_dir, committed_gen(snapshot_dir) if group is None else 0):
                 Wal.repair(path)
-                for ids, pls, vecs in Wal.replay(path, dim):
-                    self._upsert_nolog(ids, vecs, pls)
-                    m += len(ids)
+                for op in Wal.replay_ops(path, dim):
+                    if op[0] == "delete":
+                        self._delete_nolog(op[1])
+                    else:
+                        self._upsert_nolog(op[1], op[3], op[2])
+                    m += len(op[1])
             self.boot_s = {"snapshot_load_s": round(t1 - t0, 3),
                            "wal_replay_s": round(time.perf_counter() - t1, 3)}
             log.info("[INDEX_RESTORE] snapshot rows=%d (%.2fs), WAL replayed=%d (%.2fs)", n,
@@ -133,6 +136,70 @@ class VectorStore:
     @property
     def count(self) -> int:
         return self.group.count if self.group is not None else self.shard.count
+
+    @property
+    def live_count(self) -> int:
+        """Points a search can return: ``count`` (the physical rows) less the deleted ones."""
+        if self.group is not None:
+            return self.group.count
+        return self.shard.live_count
+
+    def _delete_nolog(self, point_ids) -> int:
+        id_to_row = self.shard.payloads.id_to_row
+        rows = [id_to_row[p] for p in point_ids if p in id_to_row]
+        if self._streams is not None:
+            self._rw.acquire_write()
+            try:
+                # the zeroing must not land under a pipelined search's pre-pass or scan
+                cur = torch.cuda.current_stream(self.shard.device)
+                cur.wait_stream(self._streams[0])
+                cur.wait_stream(self._streams[1])
+                n = self.shard.delete_points(point_ids)
+            finally:
+                self._rw.release_write()
+        else:
+            n = self.shard.delete_points(point_ids)
+        for r in rows:
+            self._frag.pop(r, None)
+        self._masks.clear()      # every cached mask may allow a row that is now dead
+        return n
+
+    def delete(self, point_ids: list[str] | None = None, filter: Filter | None = None) -> int:
+        """Delete points by id or by filter (exactly one of the two); returns the number of
+        points deleted.  Unknown ids are ignored.  A filter is evaluated to rows and the points of
+        the passing rows are deleted; passing rows that carry no point id (rows appended without
+        one) are skipped, since the log records a delete by point id.  wait=true semantics:
+        durable and in effect for every later search on return.  A deleted id may be upserted
+        again (it gets a new row); a dead row is never reused."""
+        if (point_ids is None) == (filter is None):
+            raise ValueError("delete takes exactly one of point_ids and filter")
+        if self.group is not None:
+            raise ValueError("delete is single-shard for now: this store writes a multi-GPU group")
+        if filter is not None and not isinstance(filter, Filter):
+            raise TypeError(f"filter must be an index.filter.Filter, got {type(filter).__name__}")
+        with self._lock:
+            ps = self.shard.payloads
+            if filter is not None:
+                hit = filter.evaluate(ps, self.shard.visible)
+                if hit.dtype == np.bool_:   # (must_not alone: walk the points, not every row)
+                    point_ids = [pid for r, pid in sorted(ps.point_ids.items())
+                                 if r < hit.size and hit[r]]
+                else:
+                    point_ids = [ps.point_ids[r] for r in hit.tolist() if r in ps.point_ids]
+            else:
+                point_ids = [p for p in dict.fromkeys(point_ids) if p in ps.id_to_row]
+            if not point_ids:
+                return 0
+            if self.wal is not None:
+                self.wal.append_delete(point_ids)
+            n = self._delete_nolog(point_ids)
+            if self.shard.device.type == "cuda":
+                torch.cuda.synchronize(self.shard.device)
+            self._since_snapshot += n
+            if (self.wal is not None and self._since_snapshot >= self.snapshot_every
+                    and not self.snapshot_running()):
+                self._start(self._cut_locked(), background=True)
+            return n
 
     def _upsert_nolog(self, point_ids, vecs, payloads):
         t = torch.as_tensor(np.ascontiguousarray(vecs, dtype=np.float32))

@@ -280,11 +280,13 @@ def filter_tiles(mask_words: torch.Tensor, n_valid: int):
 def index_scan_filter(rows: torch.Tensor, n_valid: int, mask_words: torch.Tensor,
                       tiles: torch.Tensor, n_live: torch.Tensor, q_unit: torch.Tensor, kmax: int,
                       n_rblk: int, cand_s: torch.Tensor, cand_i: torch.Tensor,
-                      thr_init: torch.Tensor | None = None, stride: int = 1, xcd: int = 1) -> None:
+                      thr_init: torch.Tensor | None = None, stride: int = 1, xcd: int = 1,
+                      gate: torch.Tensor | None = None) -> None:
     """The masked list scan: candidates [NQ][n_rblk][lists][kmax] (``topk_geometry``) of the
     allowed rows below ``n_valid``, for ``topk_merge``.  ``tiles`` / ``n_live`` are
     ``filter_tiles(mask_words, n_valid)``; ``stride`` walks every stride-th live tile of each
-    workgroup's slice only (a seed pass)."""
+    workgroup's slice only (a seed pass).  ``gate`` (int32 device flag): the scan runs only if
+    it is non-zero, and leaves the candidates untouched otherwise."""
     _chk(rows, torch.bfloat16, "rows", 2)
     _chk(q_unit, torch.bfloat16, "q_unit", 2)
     _chk(mask_words, torch.int64, "mask_words", 1)
@@ -311,9 +313,11 @@ def index_scan_filter(rows: torch.Tensor, n_valid: int, mask_words: torch.Tensor
         _chk(thr_init, torch.float32, "thr_init", 1)
         if thr_init.numel() < NQ:
             raise ValueError("index_scan_filter: thr_init shorter than the batch")
+    if gate is not None:
+        _chk(gate, torch.int32, "gate", 1)
     hip().index_scan_filter(_ptr(rows), n_valid, D, _ptr(tiles), _ptr(n_live), _ptr(mask_words),
                             stride, n_rblk, _ptr(q_unit), NQ, kmax, _ptr(cand_s), _ptr(cand_i),
-                            stream_handle(rows.device), _ptr(thr_init), xcd)
+                            stream_handle(rows.device), _ptr(thr_init), xcd, _ptr(gate))
 
 
 FILTER_FP8_DIMS = (256, 384, 512, 768, 1024)   # ... of its e4m3 form (index_filter_fp8.hip)
@@ -323,11 +327,11 @@ def index_scan_filter_fp8(rows_u8: torch.Tensor, n_valid: int, mask_words: torch
                           tiles: torch.Tensor, n_live: torch.Tensor, q_e4m3: torch.Tensor,
                           kmax: int, n_rblk: int, cand_s: torch.Tensor, cand_i: torch.Tensor,
                           thr_init: torch.Tensor | None = None, stride: int = 1,
-                          xcd: int = 1) -> None:
+                          xcd: int = 1, gate: torch.Tensor | None = None) -> None:
     """The masked list scan over e4m3 rows (``quant_fp8`` bytes at FP8_SCALE) for e4m3 queries:
     candidates [NQ][n_rblk][2][kmax] of the allowed rows below ``n_valid``, for ``topk_merge``.
     Scores are raw accumulators (FP8_SCALE**2 * cosine) and ``thr_init`` is in the same units.
-    ``tiles`` / ``n_live`` / ``stride`` as in ``index_scan_filter``."""
+    ``tiles`` / ``n_live`` / ``stride`` / ``gate`` as in ``index_scan_filter``."""
     if rows_u8.dtype != torch.uint8 or q_e4m3.dtype != torch.uint8:
         # (a bf16 slab of the same width would be read as twice as many e4m3 rows)
         raise ValueError("index_scan_filter_fp8: rows and queries are e4m3 bytes (uint8), got "
@@ -358,7 +362,56 @@ def index_scan_filter_fp8(rows_u8: torch.Tensor, n_valid: int, mask_words: torch
         _chk(thr_init, torch.float32, "thr_init", 1)
         if thr_init.numel() < NQ:
             raise ValueError("index_scan_filter_fp8: thr_init shorter than the batch")
+    if gate is not None:
+        _chk(gate, torch.int32, "gate", 1)
     hip().index_scan_filter_fp8(_ptr(rows_u8), n_valid, D, _ptr(tiles), _ptr(n_live),
                                 _ptr(mask_words), stride, n_rblk, _ptr(q_e4m3), NQ, kmax,
                                 _ptr(cand_s), _ptr(cand_i), stream_handle(rows_u8.device),
-                                _ptr(thr_init), xcd)
+                                _ptr(thr_init), xcd, _ptr(gate))
+
+
+def tombstone_rows(rows_list: torch.Tensor, n_valid: int, dead_words: torch.Tensor,
+                   slab: torch.Tensor, slab2: torch.Tensor | None = None) -> None:
+    """Tombstone the listed rows (index_delete.hip): zeros over each row of ``slab`` (and of
+    ``slab2``, e.g. a shard's e4m3 prefilter image) and the row's bit set in ``dead_words`` (int64,
+    bit r % 64 of word r // 64, as a RowMask packs).  ``rows_list``: distinct int32 rows on the
+    device; entries outside [0, n_valid) are skipped.  Slabs are [>= n_valid, D] of 1- or 2-byte
+    elements, D a multiple of 8."""
+    _chk(rows_list, torch.int32, "rows_list", 1)
+    _chk(dead_words, torch.int64, "dead_words", 1)
+    n_valid = int(n_valid)
+    D = slab.shape[-1]
+    for name, t in (("slab", slab), ("slab2", slab2)):
+        if t is None:
+            continue
+        if t.element_size() not in (1, 2):
+            raise TypeError(f"tombstone_rows: {name} must hold 1- or 2-byte elements, got {t.dtype}")
+        _chk(t, t.dtype, name, 2)
+        # the list cannot name a row past the slab: every row below n_valid lies inside it
+        if t.shape[1] != D or D % 8 or t.shape[0] < n_valid or t.device != rows_list.device:
+            raise ValueError(f"tombstone_rows: {name} {tuple(t.shape)} does not hold {n_valid} "
+                             f"rows of width {D} (a multiple of 8) on {rows_list.device}")
+    if n_valid < 0 or (n_valid + 63) // 64 > dead_words.numel():
+        raise ValueError(f"tombstone_rows: {dead_words.numel()} bitmap words do not cover "
+                         f"{n_valid} rows")
+    if dead_words.device != rows_list.device:
+        raise ValueError("tombstone_rows: bitmap and row list on different devices")
+    hip().tombstone_rows(_ptr(rows_list), rows_list.numel(), n_valid, _ptr(slab),
+                         slab.element_size(), _ptr(slab2),
+                         0 if slab2 is None else slab2.element_size(), D, _ptr(dead_words),
+                         stream_handle(rows_list.device))
+
+
+def results_dead(ids: torch.Tensor, dead_words: torch.Tensor, hits: torch.Tensor) -> None:
+    """``hits[0]`` += the number of entries of ``ids`` (int32, a search's [NQ, k] rows) that are
+    >= 0 and set in the ``dead_words`` bitmap (int64); the caller zeroes ``hits`` (int32 [1]).
+    ``-1`` ids and ids past the bitmap count nothing.  Nothing is read back."""
+    _chk(ids, torch.int32, "ids")
+    _chk(dead_words, torch.int64, "dead_words", 1)
+    _chk(hits, torch.int32, "hits", 1)
+    if hits.numel() < 1:
+        raise ValueError("results_dead: hits must hold one int32")
+    if ids.device != dead_words.device or ids.device != hits.device:
+        raise ValueError("results_dead: ids, bitmap and flag on different devices")
+    hip().results_dead(_ptr(ids), ids.numel(), _ptr(dead_words), dead_words.numel(), _ptr(hits),
+                       stream_handle(ids.device))

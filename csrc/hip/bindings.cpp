@@ -85,13 +85,19 @@ int symb_filter_tiles(const void* mask, int n_words, int n_valid, int* blk_cnt, 
 int symb_index_scan_filter(const void* X, int n_valid, int D, const int* tiles, const int* n_live,
                            const void* mask, int stride, int n_rblk, const void* Q, int NQ,
                            int kmax, float* cand_s, int* cand_i, hipStream_t st,
-                           const float* thr_init, int xcd);
+                           const float* thr_init, int xcd, const int* gate = nullptr);
 // ... over e4m3 rows (index_filter_fp8.hip)
 int symb_index_scan_filter_fp8(const void* X, int n_valid, int D, const int* tiles,
                                const int* n_live, const void* mask, int stride, int n_rblk,
                                const void* Q, int NQ, int kmax, float* cand_s, int* cand_i,
-                               hipStream_t st, const float* thr_init, int xcd);
+                               hipStream_t st, const float* thr_init, int xcd,
+                               const int* gate = nullptr);
 int symb_filter_fp8_ring_depth(int D);
+// tombstones (index_delete.hip)
+int symb_tombstone_rows(const int* rows, int n, int n_valid, void* slab0, int es0, void* slab1,
+                        int es1, int D, void* dead, hipStream_t st);
+int symb_results_dead(const int* ids, int n, const void* dead, int n_words, int* hits,
+                      hipStream_t st);
 int symb_mq_queries_per_blk(int sets, int rsplit);
 int symb_i8_queries_per_blk(int rsplit);
 int symb_index_scan_i8(const void* X8, const float* sx, int n_valid, int alloc_rows,
@@ -887,29 +893,42 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("tiles"), py::arg("n_live"), py::arg("stream"));
   m.def("index_scan_filter", [](uptr X, int n_valid, int D, uptr tiles, uptr n_live, uptr mask,
                                 int stride, int n_rblk, uptr Q, int NQ, int kmax, uptr cand_s,
-                                uptr cand_i, uptr st, uptr thr, int xcd) {
+                                uptr cand_i, uptr st, uptr thr, int xcd, uptr gate) {
     check(symb_index_scan_filter(P<void>(X), n_valid, D, P<const int>(tiles),
                                  P<const int>(n_live), P<void>(mask), stride, n_rblk, P<void>(Q),
                                  NQ, kmax, P<float>(cand_s), P<int>(cand_i), S(st),
-                                 P<const float>(thr), xcd),
+                                 P<const float>(thr), xcd, P<const int>(gate)),
           "index_scan_filter");
   }, py::arg("X"), py::arg("n_valid"), py::arg("D"), py::arg("tiles"), py::arg("n_live"),
      py::arg("mask"), py::arg("stride"), py::arg("n_rblk"), py::arg("Q"), py::arg("NQ"),
      py::arg("kmax"), py::arg("cand_s"), py::arg("cand_i"), py::arg("stream"),
-     py::arg("thr_init") = 0, py::arg("xcd") = 1);
+     py::arg("thr_init") = 0, py::arg("xcd") = 1, py::arg("gate") = 0);
   m.def("filter_fp8_ring_depth", &symb_filter_fp8_ring_depth, py::arg("D"));
   m.def("index_scan_filter_fp8", [](uptr X, int n_valid, int D, uptr tiles, uptr n_live,
                                     uptr mask, int stride, int n_rblk, uptr Q, int NQ, int kmax,
-                                    uptr cand_s, uptr cand_i, uptr st, uptr thr, int xcd) {
+                                    uptr cand_s, uptr cand_i, uptr st, uptr thr, int xcd,
+                                    uptr gate) {
     check(symb_index_scan_filter_fp8(P<void>(X), n_valid, D, P<const int>(tiles),
                                      P<const int>(n_live), P<void>(mask), stride, n_rblk,
                                      P<void>(Q), NQ, kmax, P<float>(cand_s), P<int>(cand_i),
-                                     S(st), P<const float>(thr), xcd),
+                                     S(st), P<const float>(thr), xcd, P<const int>(gate)),
           "index_scan_filter_fp8");
   }, py::arg("X"), py::arg("n_valid"), py::arg("D"), py::arg("tiles"), py::arg("n_live"),
      py::arg("mask"), py::arg("stride"), py::arg("n_rblk"), py::arg("Q"), py::arg("NQ"),
      py::arg("kmax"), py::arg("cand_s"), py::arg("cand_i"), py::arg("stream"),
-     py::arg("thr_init") = 0, py::arg("xcd") = 1);
+     py::arg("thr_init") = 0, py::arg("xcd") = 1, py::arg("gate") = 0);
+  m.def("tombstone_rows", [](uptr rows, int n, int n_valid, uptr slab0, int es0, uptr slab1,
+                             int es1, int D, uptr dead, uptr st) {
+    check(symb_tombstone_rows(P<const int>(rows), n, n_valid, P<void>(slab0), es0, P<void>(slab1),
+                              es1, D, P<void>(dead), S(st)),
+          "tombstone_rows");
+  }, py::arg("rows"), py::arg("n"), py::arg("n_valid"), py::arg("slab0"), py::arg("es0"),
+     py::arg("slab1"), py::arg("es1"), py::arg("D"), py::arg("dead"), py::arg("stream"));
+  m.def("results_dead", [](uptr ids, int n, uptr dead, int n_words, uptr hits, uptr st) {
+    check(symb_results_dead(P<const int>(ids), n, P<void>(dead), n_words, P<int>(hits), S(st)),
+          "results_dead");
+  }, py::arg("ids"), py::arg("n"), py::arg("dead"), py::arg("n_words"), py::arg("hits"),
+     py::arg("stream"));
   m.def("topk_merge", [](uptr cand_s, uptr cand_i, int NQ, int n_cand, int kmax, int k,
                          uptr out_s, uptr out_i, int64_t id_offset, uptr out_id64, uptr st,
                          uptr gate) {

@@ -98,7 +98,11 @@ __global__ __launch_bounds__(512) void index_scan_filter_kernel(
     const __bf16* __restrict__ X, int n_valid, const int* __restrict__ tiles,
     const int* __restrict__ n_live_p, const uint64_t* __restrict__ mask, int stride,
     const __bf16* __restrict__ Q, int NQ, int n_qblk, int xcd, const float* __restrict__ thr_init,
-    float* __restrict__ cand_s, int* __restrict__ cand_i) {
+    float* __restrict__ cand_s, int* __restrict__ cand_i, const int* __restrict__ gate) {
+  // gate (optional): run only if *gate != 0 -- the exact fallback of a search over a shard with
+  // tombstones (index_delete.hip) is enqueued unconditionally and skips itself unless the
+  // unmasked route returned a dead row, so no host sync decides it (as index_topk.hip)
+  if (gate != nullptr && *gate == 0) return;
   constexpr int CPR = D / 8;                          // 16-byte chunks per row
   constexpr int SUB = MFMA_32 ? 32 : 16;              // rows per MFMA chain (sub-tile)
   constexpr int TR = 2 * SUB;                         // rows per barrier interval
@@ -314,13 +318,13 @@ template <int D, bool M32, int KMAX, int NS, int AUX>
 static int launch_filter(const void* X, int n_valid, const int* tiles, const int* n_live,
                          const void* mask, int stride, int n_rblk, const void* Q, int NQ,
                          int n_qblk, int xcd, const float* thr, float* cs, int* ci,
-                         hipStream_t st) {
+                         hipStream_t st, const int* gate) {
   auto kern = index_scan_filter_kernel<D, M32, KMAX, NS, AUX>;
   constexpr int lds = NS * (M32 ? 64 : 32) * D * 2;
   set_max_lds<index_scan_filter_kernel<D, M32, KMAX, NS, AUX>>(lds);
   hipLaunchKernelGGL(kern, dim3(n_rblk * n_qblk), dim3(512), lds, st, (const __bf16*)X, n_valid,
                      tiles, n_live, (const uint64_t*)mask, stride, (const __bf16*)Q, NQ, n_qblk,
-                     xcd, thr, cs, ci);
+                     xcd, thr, cs, ci, gate);
   return (int)hipGetLastError();
 }
 
@@ -328,8 +332,8 @@ template <int D, bool M32, int NS>
 static int filter_dispatch(int kmax, int aux, const void* X, int n_valid, const int* tiles,
                            const int* n_live, const void* mask, int stride, int n_rblk,
                            const void* Q, int NQ, int n_qblk, int xcd, const float* thr, float* cs,
-                           int* ci, hipStream_t st) {
-#define SYMB_L(K, A) launch_filter<D, M32, K, NS, A>(X, n_valid, tiles, n_live, mask, stride, n_rblk, Q, NQ, n_qblk, xcd, thr, cs, ci, st)
+                           int* ci, hipStream_t st, const int* gate) {
+#define SYMB_L(K, A) launch_filter<D, M32, K, NS, A>(X, n_valid, tiles, n_live, mask, stride, n_rblk, Q, NQ, n_qblk, xcd, thr, cs, ci, st, gate)
   if (kmax == 16) return aux ? SYMB_L(16, 2) : SYMB_L(16, 0);
   return aux ? SYMB_L(32, 2) : SYMB_L(32, 0);
 #undef SYMB_L
@@ -340,17 +344,18 @@ static int filter_dispatch(int kmax, int aux, const void* X, int n_valid, const 
 // below ceil(n_valid / 64)); mask: the words filter_tiles read.
 // cand_*: [NQ][n_rblk][lists][kmax] (symb_topk_geometry), merged by symb_topk_merge.
 // stride >= 1: walk every stride-th entry of each workgroup's slice.
+// gate (optional, device int): the scan runs only if *gate != 0.
 int symb_index_scan_filter(const void* X, int n_valid, int D, const int* tiles, const int* n_live,
                            const void* mask, int stride, int n_rblk, const void* Q, int NQ,
                            int kmax, float* cand_s, int* cand_i, hipStream_t st,
-                           const float* thr_init, int xcd) {
+                           const float* thr_init, int xcd, const int* gate) {
   if (NQ <= 0 || n_rblk <= 0) return 0;
   if (stride < 1 || n_valid < 0 || (kmax != 16 && kmax != 32)) return -1;
   if (!tiles || !n_live || !mask) return -1;
   const int qpb = D == 384 ? 256 : 128;
   const int n_qblk = (NQ + qpb - 1) / qpb;
   const int aux = n_qblk == 1 ? 2 : 0;   // non-temporal when each index row is read by one block
-#define SYMB_ARGS kmax, aux, X, n_valid, tiles, n_live, mask, stride, n_rblk, Q, NQ, n_qblk, xcd, thr_init, cand_s, cand_i, st
+#define SYMB_ARGS kmax, aux, X, n_valid, tiles, n_live, mask, stride, n_rblk, Q, NQ, n_qblk, xcd, thr_init, cand_s, cand_i, st, gate
   if (D == 384) return filter_dispatch<384, true, 3>(SYMB_ARGS);
   if (D == 768) return filter_dispatch<768, false, 3>(SYMB_ARGS);
   if (D == 1024) return filter_dispatch<1024, false, 2>(SYMB_ARGS);

@@ -41,7 +41,9 @@ __global__ __launch_bounds__(256, 1) void index_scan_filter_fp8_kernel(
     const uint8_t* __restrict__ X, int n_valid, const int* __restrict__ tiles,
     const int* __restrict__ n_live_p, const uint64_t* __restrict__ mask, int stride,
     const uint8_t* __restrict__ Q, int NQ, int n_qblk, int xcd, const float* __restrict__ thr_init,
-    float* __restrict__ cand_s, int* __restrict__ cand_i) {
+    float* __restrict__ cand_s, int* __restrict__ cand_i, const int* __restrict__ gate) {
+  // gate (optional): run only if *gate != 0 (index_filter.hip has the note)
+  if (gate != nullptr && *gate == 0) return;
   constexpr int CPR = D / 16, SUB = 32, TR = 32 * SUBS, NW = 4;
   constexpr int IPE = 64 / TR;                     // barrier intervals per list entry
   constexpr int TILE_BYTES = TR * D, SUB_BYTES = SUB * D;
@@ -252,14 +254,14 @@ template <int D, int KMAX, int AUX>
 static int launch_filter_fp8(const void* X, int n_valid, const int* tiles, const int* n_live,
                              const void* mask, int stride, int n_rblk, const void* Q, int NQ,
                              int n_qblk, int xcd, const float* thr, float* cs, int* ci,
-                             hipStream_t st) {
+                             hipStream_t st, const int* gate) {
   constexpr int SUBS = Fp8Cfg<D>::SUBS, NS = Fp8Cfg<D>::NS;
   auto kern = index_scan_filter_fp8_kernel<D, KMAX, NS, SUBS, AUX>;
   constexpr int lds = NS * 32 * SUBS * D;
   set_max_lds<index_scan_filter_fp8_kernel<D, KMAX, NS, SUBS, AUX>>(lds);
   hipLaunchKernelGGL(kern, dim3(n_rblk * n_qblk), dim3(256), lds, st, (const uint8_t*)X, n_valid,
                      tiles, n_live, (const uint64_t*)mask, stride, (const uint8_t*)Q, NQ, n_qblk,
-                     xcd, thr, cs, ci);
+                     xcd, thr, cs, ci, gate);
   return (int)hipGetLastError();
 }
 
@@ -267,8 +269,8 @@ template <int D>
 static int filter_fp8_dispatch(int kmax, int aux, const void* X, int n_valid, const int* tiles,
                                const int* n_live, const void* mask, int stride, int n_rblk,
                                const void* Q, int NQ, int n_qblk, int xcd, const float* thr,
-                               float* cs, int* ci, hipStream_t st) {
-#define SYMB_L(K, A) launch_filter_fp8<D, K, A>(X, n_valid, tiles, n_live, mask, stride, n_rblk, Q, NQ, n_qblk, xcd, thr, cs, ci, st)
+                               float* cs, int* ci, hipStream_t st, const int* gate) {
+#define SYMB_L(K, A) launch_filter_fp8<D, K, A>(X, n_valid, tiles, n_live, mask, stride, n_rblk, Q, NQ, n_qblk, xcd, thr, cs, ci, st, gate)
   if (kmax == 16) return aux ? SYMB_L(16, 2) : SYMB_L(16, 0);
   return aux ? SYMB_L(32, 2) : SYMB_L(32, 0);
 #undef SYMB_L
@@ -295,13 +297,14 @@ int symb_filter_fp8_ring_depth(int D) {
 int symb_index_scan_filter_fp8(const void* X, int n_valid, int D, const int* tiles,
                                const int* n_live, const void* mask, int stride, int n_rblk,
                                const void* Q, int NQ, int kmax, float* cand_s, int* cand_i,
-                               hipStream_t st, const float* thr_init, int xcd) {
+                               hipStream_t st, const float* thr_init, int xcd,
+                               const int* gate) {
   if (NQ <= 0 || n_rblk <= 0) return 0;
   if (stride < 1 || n_valid < 0 || (kmax != 16 && kmax != 32)) return -1;
   if (!tiles || !n_live || !mask) return -1;
   const int n_qblk = (NQ + 255) / 256;
   const int aux = n_qblk == 1 ? 2 : 0;   // non-temporal when each index row is read by one block
-#define SYMB_ARGS kmax, aux, X, n_valid, tiles, n_live, mask, stride, n_rblk, Q, NQ, n_qblk, xcd, thr_init, cand_s, cand_i, st
+#define SYMB_ARGS kmax, aux, X, n_valid, tiles, n_live, mask, stride, n_rblk, Q, NQ, n_qblk, xcd, thr_init, cand_s, cand_i, st, gate
   switch (D) {
     case 256: return filter_fp8_dispatch<256>(SYMB_ARGS);
     case 384: return filter_fp8_dispatch<384>(SYMB_ARGS);
