@@ -21,9 +21,14 @@ Every line carries ``last_dead_hits`` (must be 0: each query keeps k live rows s
 ``rows_equal_mask`` (the result against the masked scan's: same rows outside runs of equal scores)
 and ``max_abs_vs_mask``; the ``delete`` lines carry the cost of the delete itself per 1k rows.
 
+k > 32 (bf16 shards: the masked emitting scan, index_mq_filter.hip, is the masked route): the
+``mask`` line also carries ``overflow`` (its candidate-overflow flag: 1 = it fell back to the
+masked matmul) and ``max_candidates``; --fallback adds ``matmul_mask``, one iteration of the
+chunked matmul under ~dead, the route of such a search before the masked emitting scan.
+
     python benchmarks/delete_bench.py [--rows 100000000] [--dim 384] [--dtype bf16|fp8]
         [--prune i8|none] [--pattern uniform|docs] [--levels 0.01,1,10] [--nq 256] [--k 10]
-        [--rounds 3] [--iters 5] [--out FILE]
+        [--rounds 3] [--iters 5] [--out FILE] [--fallback]
 """
 from __future__ import annotations
 
@@ -86,6 +91,8 @@ def main() -> None:
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--fallback", action="store_true",
+                    help="also time the chunked matmul under ~dead (one iteration per level)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("delete_bench needs the GPU: nothing here is measured without one")
@@ -115,11 +122,15 @@ def main() -> None:
 
     def run(variants: dict, info: dict, ref=None) -> dict:
         """Alternated rounds of every variant; one line each; returns (medians, all times)."""
-        res, hits = {}, {}
+        res, hits, large = {}, {}, {}
         for v, fn in variants.items():               # results first (also the warm-up)
             shard.last_dead_hits = None
+            shard._filter_large_k_last = None
             res[v] = fn()
             hits[v] = 0 if shard.last_dead_hits is None else int(shard.last_dead_hits)
+            last = shard._filter_large_k_last
+            if v == "mask" and last is not None:
+                large[v] = {"overflow": int(last[1]), "max_candidates": int(last[0].max())}
         torch.cuda.synchronize()
         times = {v: [] for v in variants}
         for _ in range(a.rounds):
@@ -134,7 +145,8 @@ def main() -> None:
                          "max_abs_vs_mask": float((s - ref[0]).abs().max())}
             med[v] = statistics.median(ts)
             emit(dict(info, variant=v, ms=round(med[v], 3), ms_min=round(min(ts), 3),
-                      ms_max=round(max(ts), 3), last_dead_hits=hits[v], **extra))
+                      ms_max=round(max(ts), 3), last_dead_hits=hits[v], **extra,
+                      **large.get(v, {})))
         return med, times
 
     def search(route):
@@ -164,6 +176,10 @@ def main() -> None:
         torch.cuda.synchronize()
         med, _ = run({"route_only": lambda: shard._search_route(q, k, None),
                       "zero": lambda: search("zero"), "mask": lambda: search("mask")}, info, ref)
+        if a.fallback:
+            ms = timed(lambda: shard._search_matmul(q, k, mask=shard._live()), 1)
+            emit(dict(info, variant="matmul_mask", ms=round(ms, 3), ms_min=round(ms, 3),
+                      ms_max=round(ms, 3), iters=1, rounds=1))
         over = med["zero"] - med["route_only"]
         emit(dict(info, variant="summary", no_delete_ms=round(plain["search_a"], 3),
                   no_delete_spread_ms=round(spread, 3), zero_overhead_ms=round(over, 3),

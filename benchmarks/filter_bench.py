@@ -14,6 +14,12 @@ Per mask, in alternated rounds on the same shard (one JSON line per mask and var
   matmul_mask      (--fallback) the chunked matmul under the mask, the route of every shard the
                    masked scan does not serve and of fp8 shards before it did: one iteration
 
+k > 32 (the masked emitting scan, index_mq_filter.hip, on bf16 shards): the list scans stop at
+kmax = 32, so the variants are ``filtered`` (shard.search(q, k, allow=mask)) and ``search`` (the
+unfiltered top-k), plus matmul_mask with --fallback; every ``filtered`` line carries ``overflow``
+(the route's candidate-overflow flag: 1 means the search fell back to the masked matmul) and
+``max_candidates`` (the most candidates one query emitted).
+
 --dtype fp8: the shard holds e4m3 rows, gather_scan is the fp8 list scan over the index_select-ed
 bytes, and every record carries "dtype": "fp8", rows_equal_gather (the masked scan's rows against
 gather_scan's: equal outside runs of equal scores, and a last slot that differs without an equal
@@ -163,7 +169,8 @@ def main() -> None:
         m = idx.numel()
         m_pad = (m + TILE_ROWS - 1) // TILE_ROWS * TILE_ROWS
         free, _ = torch.cuda.mem_get_info(dev)
-        gather_ok = m > 0 and m_pad * row_bytes < free - (8 << 30)
+        large_k = k > 32                   # no list scan at this k: filtered / search only
+        gather_ok = not large_k and m > 0 and m_pad * row_bytes < free - (8 << 30)
         sub = (torch.zeros(m_pad, a.dim, dtype=shard.rows.dtype, device=dev) if gather_ok
                else None)
 
@@ -186,11 +193,22 @@ def main() -> None:
                     "plain_scan": lambda: shard._scan(n, q8 if fp8 else q, kmax, k, None, None)}
         if gather_ok:
             variants["gather_scan"] = gather
+        if large_k:
+            variants = {"filtered": lambda: shard.search(q, k, allow=mask),
+                        "search": lambda: shard.search(q, k)}
         # results first (also the warm-up of every shape): seed on == seed off == gather
+        shard._filter_large_k_last = None
         res = {v: fn() for v, fn in variants.items()}
         torch.cuda.synchronize()
-        same_seed = bool(torch.equal(res["filtered_seed"][0], res["filtered_noseed"][0])
-                         and torch.equal(res["filtered_seed"][1], res["filtered_noseed"][1]))
+        same_seed, per_variant = None, {}
+        if large_k:
+            last = getattr(shard, "_filter_large_k_last", None)
+            if last is not None:
+                per_variant["filtered"] = {"overflow": int(last[1]),
+                                           "max_candidates": int(last[0].max())}
+        else:
+            same_seed = bool(torch.equal(res["filtered_seed"][0], res["filtered_noseed"][0])
+                             and torch.equal(res["filtered_seed"][1], res["filtered_noseed"][1]))
         same_gather = None
         if gather_ok:
             same_gather = bool(torch.equal(res["filtered_seed"][0], res["gather_scan"][0]))
@@ -210,7 +228,8 @@ def main() -> None:
         for v, ts in times.items():
             emit(dict(info, variant=v, ms=round(statistics.median(ts), 3),
                       ms_min=round(min(ts), 3), ms_max=round(max(ts), 3),
-                      seed_on_equals_off=same_seed, scores_equal_gather=same_gather, **extra))
+                      seed_on_equals_off=same_seed, scores_equal_gather=same_gather, **extra,
+                      **per_variant.get(v, {})))
         if a.fallback:
             ms = timed(lambda: shard._search_matmul(q, k, mask=mask), 1)
             emit(dict(info, variant="matmul_mask", ms=round(ms, 3), ms_min=round(ms, 3),

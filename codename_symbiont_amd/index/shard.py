@@ -203,6 +203,20 @@ I8_RING_DIMS = (768,)
 
 FILTER_DIMS = (384, 768, 1024)          # ... the masked list scan (index_filter.hip)
 FILTER_FP8_DIMS = (256, 384, 512, 768, 1024)   # ... its e4m3 form (index_filter_fp8.hip)
+FILTER_LARGE_K_DIMS = (384, 768, 1024)  # ... the masked emitting scan (index_mq_filter.hip)
+
+
+def filter_large_k_threshold(cand_s: torch.Tensor, k: int, margin: float) -> torch.Tensor:
+    """Per-query threshold of the masked large-k search from a seed pass's candidate block
+    ``cand_s`` [NQ, m]: the k-th largest FINITE entry less ``margin``, -inf where fewer than k
+    entries are finite.  Every finite entry is a distinct allowed row's real score, so the k-th
+    best of them is a lower bound on the k-th best allowed score."""
+    NQ, m = cand_s.shape
+    if m < k:
+        return torch.full((NQ,), -math.inf, dtype=torch.float32, device=cand_s.device)
+    s = torch.where(torch.isfinite(cand_s), cand_s, torch.full_like(cand_s, -math.inf))
+    kth = torch.topk(s, k, dim=1).values[:, k - 1]
+    return (kth - margin).float().contiguous()
 
 
 def _pack_bits(allow: torch.Tensor, n_words: int) -> torch.Tensor:
@@ -376,6 +390,8 @@ class HbmIndexShard:
         # masked search (_search_filtered): a stride-64 pass over the live tiles first, whose k-th
         # best allowed score seeds the full pass's thresholds (FILTER_SEED_DEFAULT has the A/B)
         self.filter_seed = self.FILTER_SEED_DEFAULT
+        # (candidate counts, overflow flag) of the last masked large-k search (tests, benchmarks)
+        self._filter_large_k_last = None
         # > 256 queries: put the query blocks of each row block on one XCD (row stream shared
         # through that XCD's L2 instead of re-read from HBM once per query block)
         self.scan_xcd = 1
@@ -1067,7 +1083,7 @@ class HbmIndexShard:
             if v < nw * 64:      # bits at or past ``visible`` are clear in a RowMask
                 words[v // 64:v // 64 + 1].bitwise_and_((1 << (v % 64)) - 1)
             tiles = n_live = None
-            if self.device.type == "cuda" and self._filter_scan_serves():
+            if self.device.type == "cuda" and self._mask_tiles_wanted():
                 from ..ops.kernels import filter_tiles
 
                 tiles, n_live = filter_tiles(words, v)
@@ -1094,6 +1110,10 @@ class HbmIndexShard:
         returned; the search is exact over them (_search_masked).
 
         Tombstoned rows (``delete_rows``) are never returned (_search_tombstoned).
+
+        On a bf16 GPU shard of width 384 / 768 / 1024 both run on the HIP scans up to k = 128
+        (k <= 32: the masked list scan; above: the masked emitting scan); beyond that, and on
+        shards those scans do not serve, they take the chunked matmul under the mask.
 
         Returns (scores f32 [NQ, k], rows int32 [NQ, k]); missing slots are (-inf, -1)."""
         if allow is not None:
@@ -1134,8 +1154,9 @@ class HbmIndexShard:
     def _zero_route_serves(self, NQ: int, k: int) -> bool:
         """A search over tombstones runs the unmasked route plus the gated masked scan (else:
         the masked scan or the masked matmul, directly)."""
-        return (self.delete_route == "zero" and self.device.type == "cuda" and 0 < k <= 32
-                and NQ > 0 and self._filter_scan_serves())
+        return (self.delete_route == "zero" and self.device.type == "cuda" and NQ > 0
+                and ((0 < k <= 32 and self._filter_scan_serves())
+                     or self._filter_large_k_serves(k)))
 
     def _search_tombstoned(self, q_unit: torch.Tensor, k: int, n_cus):
         """``search`` on a shard with tombstones, exact over the live rows, no host sync.
@@ -1143,17 +1164,19 @@ class HbmIndexShard:
         Every unmasked route is exact over the physical rows, and a dead row is a zero row there
         (delete_rows).  If the top-k over that superset holds no dead row it IS the top-k over
         the live rows, so: run the route unchanged, count the returned ids that are dead into a
-        device flag (results_dead), and enqueue the exact masked list scan under the live mask
+        device flag (results_dead), and enqueue the exact masked scan under the live mask (the
+        list scan at k <= 32, the emitting scan of _search_filtered_large_k at 32 < k <= 128)
         gated on that flag -- with no hit its launches exit at once -- then take
         where(hit, fallback, route).  No hit is the only outcome while every query has at least
         k live rows scoring above 0, so each route keeps its own speed after deletes.
-        ``delete_route = "mask"`` goes straight to the masked scan; CPU shards, k > 32 and widths
-        the masked scan does not serve take the masked matmul."""
+        ``delete_route = "mask"`` goes straight to the masked scan; CPU shards, k > 128, fp8
+        shards at k > 32 and widths no masked scan serves take the masked matmul."""
         NQ, k = q_unit.shape[0], int(k)
         if NQ == 0 or k <= 0:
             return self._search_route(q_unit, k, n_cus)
         live = self._live()
-        if self.device.type != "cuda" or k > 32 or not self._filter_scan_serves():
+        large_k = self._filter_large_k_serves(k)
+        if self.device.type != "cuda" or not (large_k or (k <= 32 and self._filter_scan_serves())):
             self.last_dead_hits = None
             return self._search_matmul(q_unit, k, mask=live)
         q = q_unit.to(torch.bfloat16).contiguous()
@@ -1161,6 +1184,8 @@ class HbmIndexShard:
             if self._zero_hits is None:
                 self._zero_hits = torch.zeros(1, dtype=torch.int32, device=self.device)
             self.last_dead_hits = self._zero_hits
+            if large_k:
+                return self._search_filtered_large_k(q, k, live, n_cus)
             return self._search_filtered(q, k, live, n_cus)
         out_s, out_i = self._search_route(q, k, n_cus)
         return self._dead_fallback(q, k, n_cus, live, out_s, out_i)
@@ -1172,7 +1197,8 @@ class HbmIndexShard:
 
         hit = torch.zeros(1, dtype=torch.int32, device=self.device)
         K.results_dead(out_i.contiguous(), self.dead.view(torch.int64), hit)
-        fb_s, fb_i = self._search_filtered(q, k, live, n_cus, gate=hit)
+        masked = self._search_filtered_large_k if k > 32 else self._search_filtered
+        fb_s, fb_i = masked(q, k, live, n_cus, gate=hit)
         self.last_dead_hits = hit
         take = hit > 0
         return torch.where(take, fb_s, out_s), torch.where(take, fb_i, out_i)
@@ -1259,7 +1285,7 @@ class HbmIndexShard:
         if self.n_dead:      # a tombstoned row passes no mask
             bits = (bits.view(torch.int64) & ~self.dead.view(torch.int64)[:nw]).view(torch.uint8)
         tiles = n_live = None
-        if dev.type == "cuda" and self._filter_scan_serves():
+        if dev.type == "cuda" and self._mask_tiles_wanted():
             from ..ops.kernels import filter_tiles
 
             tiles, n_live = filter_tiles(bits.view(torch.int64), v)
@@ -1270,10 +1296,22 @@ class HbmIndexShard:
         return ((self.dtype == "bf16" and self.dim in FILTER_DIMS)
                 or (self.dtype == "fp8" and self.dim in FILTER_FP8_DIMS))
 
+    def _filter_large_k_serves(self, k: int) -> bool:
+        """The masked emitting scan serves a search at this k: a bf16 shard on a GPU at a width
+        in FILTER_LARGE_K_DIMS with the emitting scan on, 32 < k <= K_MAX_HIP."""
+        return (self.device.type == "cuda" and self.dtype == "bf16" and bool(self.scan_mq)
+                and self.dim in FILTER_LARGE_K_DIMS and 32 < k <= self.K_MAX_HIP)
+
+    def _mask_tiles_wanted(self) -> bool:
+        """Some masked scan of this shard walks a RowMask's live-tile list."""
+        return self._filter_scan_serves() or self._filter_large_k_serves(self.K_MAX_HIP)
+
     def _search_masked(self, q_unit, k: int, n_cus, allow):
         """``search`` under a row mask, exact over the allowed rows.  A GPU shard at k <= 32 takes
         the masked list scan of its row format (bf16 at a width in FILTER_DIMS, fp8 at one in
-        FILTER_FP8_DIMS); everything else (CPU shards, k > 32, other widths) the chunked matmul
+        FILTER_FP8_DIMS); a bf16 GPU shard at 32 < k <= 128 and a width in FILTER_LARGE_K_DIMS the
+        masked emitting scan (_search_filtered_large_k); everything else (CPU shards, k > 128, fp8
+        shards at k > 32, other widths) the chunked matmul
         with the score block masked.  On an fp8 shard the list scan scores e4m3(q) . e4m3(x), as
         the unmasked GPU search does; the matmul scores float(q) . decode(x).  The cheap routes of
         the unmasked search do not apply: their thresholds come from a sample of ALL rows, which
@@ -1292,7 +1330,111 @@ class HbmIndexShard:
         if (self.device.type == "cuda" and self._filter_scan_serves() and k <= 32
                 and mask.tiles is not None):
             return self._search_filtered(q_unit.to(torch.bfloat16).contiguous(), k, mask, n_cus)
+        if self._filter_large_k_serves(k) and mask.tiles is not None:
+            return self._search_filtered_large_k(q_unit.to(torch.bfloat16).contiguous(), k, mask,
+                                                 n_cus)
         return self._search_matmul(q_unit, k, mask=mask)
+
+    # seed pass of the masked large-k search: every S-th live tile of each workgroup's slice.
+    # 32 is the unmasked route's sample rate (PRUNE_TILE_SHIFT = 5).  A query emits about k * S
+    # candidates (at most 1.3 k * S over 256 queries): at 100M x 384, k = 100, S = 64 is 6 %
+    # faster on the all-ones mask with 1.9x of head room to LARGE_K_CAP instead of 3.5x, and
+    # S = 128 overflows into the matmul (profiles/r11_filter_largek/ has the A/B).
+    FILTER_LARGE_K_STRIDE = 32
+    # the seed pass's own seed: every 16th tile of its sample (1: off).  100M x 384, k = 100:
+    # all-ones mask 21.6 -> 18.1 ms, documents 10 % 3.13 -> 2.73, uniform 1 % 8.51 -> 8.72 (the
+    # extra launch where the lists hardly fill); same T, same candidates (profiles/r11_filter_largek/)
+    FILTER_LARGE_K_COARSE = 16
+
+    def _mq_filter_form(self, NQ: int):
+        """(sets, rsplit) of the masked emitting scan: _mq_form's, except that at D = 384 below
+        512 queries it is always the row-split form (there is no masked (2, 1) form)."""
+        if self.dim != 384:
+            return (2 if self.dim == 768 else 1), 1
+        return (4, 1) if NQ >= 512 else (4, 2)
+
+    def _search_filtered_large_k(self, q_unit, k: int, mask: RowMask, n_cus, gate=None,
+                                 seed: bool = True):
+        """EXACT top-k over the allowed rows for 32 < k <= 128 (bf16, FILTER_LARGE_K_DIMS), at any
+        number of visible rows:
+
+        1. T[q], a lower bound on query q's final k-th ALLOWED score from allowed rows only: the
+           masked list scan (kmax 32) over every FILTER_LARGE_K_STRIDE-th live tile of each
+           workgroup's slice leaves [NQ, n_rblk * lists * 32] candidates, each a distinct allowed
+           row's real score, and T is the k-th largest finite one (-inf below k of them: a mask
+           with few allowed rows emits every one), less MQ_THR_MARGIN for the two kernels'
+           different summation orders (filter_large_k_threshold).  On shards of SEED_MIN_ROWS
+           rows or more that pass is itself seeded, by a kmax = 16 pass over every
+           FILTER_LARGE_K_COARSE-th tile of its sample, which changes its time and not T.
+           ``seed=False``: T = -inf.
+        2. the masked emitting scan (index_mq_filter.hip) over the whole list keeps every allowed
+           row above T in LARGE_K_CAP slots per query, and the radix select takes the top k:
+           descending, (-inf, -1) past the allowed rows.
+        3. a query whose candidates overflow the cap raises the select's flag (read back once,
+           as _search_large_k reads its own) and the search takes the masked matmul.
+
+        ``gate`` (int32 device flag): every launch runs only if it is non-zero; at 0 the
+        overflow flag stays 0 and the outputs hold garbage the caller never selects."""
+        from ..ops import kernels as K
+        from ..ops._ext import hip, stream_handle
+
+        h, dev = hip(), self.device
+        NQ = q_unit.shape[0]
+        n = min(mask.visible, self.visible)
+        out_s = torch.empty(NQ, k, device=dev)
+        out_i = torch.empty(NQ, k, dtype=torch.int32, device=dev)
+        if n <= 0:
+            return out_s.fill_(-math.inf), out_i.fill_(-1)
+        if n_cus is None:
+            n_cus = self._n_cus()
+        tile_slots = math.ceil(n / (TILE_ROWS * self.FILTER_MIN_TILES))
+        if seed:
+            lists, qpb = h.topk_geometry(self.dim, 32)
+            n_rblk = max(1, min(tile_slots, max(1, round(n_cus / math.ceil(NQ / qpb)))))
+            ncand = n_rblk * lists * 32
+            cs = torch.empty(NQ, ncand, device=dev)
+            ci = torch.empty(NQ, ncand, dtype=torch.int32, device=dev)
+            T0 = None
+            if self.FILTER_LARGE_K_COARSE > 1 and n >= self.SEED_MIN_ROWS:
+                # The seed pass's register lists start empty and take their first rows through
+                # the serial 32-slot insert, most of its time.  A coarser pass first (kmax = 16,
+                # every COARSE-th tile of the seed pass's own sample: the same slices, so a
+                # subset of it) gives the seed pass a threshold of its own; the seed pass's
+                # k best rows all lie above it, so T is what the unseeded seed pass gives.
+                # (Not on small shards, where its launch costs more than it saves.)
+                l16, _ = h.topk_geometry(self.dim, 16)
+                c0 = torch.empty(NQ, n_rblk * l16 * 16, device=dev)
+                i0 = torch.empty(NQ, n_rblk * l16 * 16, dtype=torch.int32, device=dev)
+                K.index_scan_filter(self.rows, n, mask.words, mask.tiles, mask.n_live, q_unit,
+                                    16, n_rblk, c0, i0, None,
+                                    self.FILTER_LARGE_K_STRIDE * self.FILTER_LARGE_K_COARSE,
+                                    self.scan_xcd, gate)
+                T0 = filter_large_k_threshold(c0, k, self.MQ_THR_MARGIN)
+            K.index_scan_filter(self.rows, n, mask.words, mask.tiles, mask.n_live, q_unit, 32,
+                                n_rblk, cs, ci, T0, self.FILTER_LARGE_K_STRIDE, self.scan_xcd,
+                                gate)
+            T = filter_large_k_threshold(cs, k, self.MQ_THR_MARGIN)
+        else:
+            T = torch.full((NQ,), -math.inf, device=dev)
+        sets, rsplit = self._mq_filter_form(NQ)
+        n_qblk = math.ceil(NQ / h.mq_queries_per_blk(sets, rsplit))
+        n_rblk = max(1, min(tile_slots, max(1, round(n_cus / n_qblk))))
+        cap = self.LARGE_K_CAP
+        es = torch.empty(NQ, cap, device=dev)
+        ei = torch.empty(NQ, cap, dtype=torch.int32, device=dev)
+        cnt = torch.empty(NQ, dtype=torch.int32, device=dev)
+        # this search's own overflow flag; zeroed here, so a closed gate leaves it 0
+        ovf = torch.zeros(1, dtype=torch.int32, device=dev)
+        K.index_scan_mq_filter(self.rows, n, mask.words, mask.tiles, mask.n_live, q_unit, T, es,
+                               ei, cnt, cap, n_rblk, sets, rsplit, self.scan_xcd, gate)
+        h.topk_select_counted(es.data_ptr(), ei.data_ptr(), cnt.data_ptr(), cap, NQ, 128, k,
+                              out_s.data_ptr(), out_i.data_ptr(), ovf.data_ptr(),
+                              stream_handle(dev), gate=0 if gate is None else gate.data_ptr(),
+                              reset_ovf=False)
+        self._filter_large_k_last = (cnt, ovf)   # candidate counts / overflow flag (tests)
+        if int(ovf.item()):
+            return self._search_matmul(q_unit, k, mask=mask)
+        return out_s, out_i
 
     def _search_filtered(self, q_unit, k: int, mask: RowMask, n_cus, gate=None):
         """The masked list scan (index_filter.hip; index_filter_fp8.hip on an fp8 shard, whose

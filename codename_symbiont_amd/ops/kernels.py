@@ -320,6 +320,62 @@ def index_scan_filter(rows: torch.Tensor, n_valid: int, mask_words: torch.Tensor
                             stream_handle(rows.device), _ptr(thr_init), xcd, _ptr(gate))
 
 
+FILTER_LARGE_K_DIMS = (384, 768, 1024)   # ... of the masked emitting scan (index_mq_filter.hip)
+# (sets, rsplit) forms it is built for, per width
+_MQ_FILTER_FORMS = {384: ((4, 1), (4, 2)), 768: ((2, 1),), 1024: ((1, 1),)}
+
+
+def index_scan_mq_filter(rows: torch.Tensor, n_valid: int, mask_words: torch.Tensor,
+                         tiles: torch.Tensor, n_live: torch.Tensor, q_unit: torch.Tensor,
+                         thr: torch.Tensor, cand_s: torch.Tensor, cand_i: torch.Tensor,
+                         cand_n: torch.Tensor, cap: int, n_rblk: int, sets: int, rsplit: int,
+                         xcd: int = 1, gate: torch.Tensor | None = None,
+                         zero_cnt: bool = True) -> None:
+    """The masked emitting scan: every allowed row below ``n_valid`` scoring above ``thr[q]`` is
+    appended to query q's candidates, ``cand_s`` / ``cand_i`` [NQ, cap] (score, physical row), and
+    counted in ``cand_n`` [NQ] -- which may exceed ``cap``; nothing is written at or past it
+    (``topk_select_counted`` raises its overflow flag then).  ``tiles`` / ``n_live`` are
+    ``filter_tiles(mask_words, n_valid)``.  ``sets`` / ``rsplit``: the kernel form (16-query sets
+    per wave, waves sharing a query group; 8 / rsplit * 16 * sets queries per workgroup); the
+    grid is ``n_rblk`` row slots per query block, sharing the live tiles evenly.  ``zero_cnt``
+    False appends to ``cand_n``.  ``gate`` (int32 device flag): scan and zeroing run only if it
+    is non-zero, and leave every buffer untouched otherwise."""
+    _chk(rows, torch.bfloat16, "rows", 2)
+    _chk(q_unit, torch.bfloat16, "q_unit", 2)
+    _chk(mask_words, torch.int64, "mask_words", 1)
+    _chk(tiles, torch.int32, "tiles", 1)
+    _chk(n_live, torch.int32, "n_live", 1)
+    _chk(thr, torch.float32, "thr", 1)
+    _chk(cand_s, torch.float32, "cand_s")
+    _chk(cand_i, torch.int32, "cand_i")
+    _chk(cand_n, torch.int32, "cand_n", 1)
+    D = rows.shape[1]
+    NQ = q_unit.shape[0]
+    n_valid, n_rblk, cap = int(n_valid), int(n_rblk), int(cap)
+    if D not in FILTER_LARGE_K_DIMS or q_unit.shape[1] != D:
+        raise ValueError(f"index_scan_mq_filter: rows must be {FILTER_LARGE_K_DIMS} wide, "
+                         "queries alike")
+    if (int(sets), int(rsplit)) not in _MQ_FILTER_FORMS[D]:
+        raise ValueError(f"index_scan_mq_filter: (sets, rsplit) at D = {D} is one of "
+                         f"{_MQ_FILTER_FORMS[D]}")
+    if n_rblk < 1 or cap < 1 or n_valid < 0 or n_live.numel() < 1:
+        raise ValueError("index_scan_mq_filter: n_rblk >= 1, cap >= 1, n_valid >= 0")
+    n_tiles = (n_valid + 63) // 64
+    # every tile the list can name lies inside the row slab and has a mask word
+    if n_tiles * 64 > rows.shape[0] or n_tiles > mask_words.numel() or n_tiles > tiles.numel():
+        raise ValueError("index_scan_mq_filter: rows / mask / tile list shorter than n_valid")
+    if thr.numel() < NQ or cand_n.numel() < NQ:
+        raise ValueError("index_scan_mq_filter: thr / cand_n shorter than the batch")
+    if cand_s.numel() < NQ * cap or cand_i.numel() < NQ * cap:
+        raise ValueError("index_scan_mq_filter: candidate workspace too small")
+    if gate is not None:
+        _chk(gate, torch.int32, "gate", 1)
+    hip().index_scan_mq_filter(_ptr(rows), n_valid, _ptr(tiles), _ptr(n_live), _ptr(mask_words),
+                               n_rblk, _ptr(q_unit), NQ, _ptr(thr), _ptr(cand_s), _ptr(cand_i),
+                               _ptr(cand_n), cap, xcd, stream_handle(rows.device), int(sets),
+                               int(rsplit), _ptr(gate), bool(zero_cnt), D)
+
+
 FILTER_FP8_DIMS = (256, 384, 512, 768, 1024)   # ... of its e4m3 form (index_filter_fp8.hip)
 
 
