@@ -26,9 +26,23 @@ k > 32 (bf16 shards: the masked emitting scan, index_mq_filter.hip, is the maske
 masked matmul) and ``max_candidates``; --fallback adds ``matmul_mask``, one iteration of the
 chunked matmul under ~dead, the route of such a search before the masked emitting scan.
 
+--compact adds, after the last level's lines (nothing above changes), the in-place compaction
+(HbmIndexShard.compact, csrc/hip/index_compact.hip) of what the levels left:
+
+  tombstoned     shard.search(q, k) under the shard's default delete route, just before
+  compact_torch  the same plan run with torch on a copy of the row slab: index_select per window
+                 plus copy_ (the route without the kernel; it needs that second slab, the int64
+                 index of every window and a bool per row); the copy is then the check of
+                 compact()'s rows, ``rows_equal``
+  compact        shard.compact() itself, plan, moves, zeroed tail and re-imaging included;
+                 ``reimage_ms`` is the re-imaging alone (run once more: it is idempotent),
+                 ``gbps`` the bytes of the rows above the first dead row over the time less that
+  compacted /    shard.search(q, k) on the compacted shard and on a fresh shard of the same rows
+  fresh          that never saw a delete, alternated (``fresh`` is skipped where both do not fit)
+
     python benchmarks/delete_bench.py [--rows 100000000] [--dim 384] [--dtype bf16|fp8]
         [--prune i8|none] [--pattern uniform|docs] [--levels 0.01,1,10] [--nq 256] [--k 10]
-        [--rounds 3] [--iters 5] [--out FILE] [--fallback]
+        [--rounds 3] [--iters 5] [--out FILE] [--fallback] [--compact]
 """
 from __future__ import annotations
 
@@ -93,6 +107,8 @@ def main() -> None:
     ap.add_argument("--out", default="")
     ap.add_argument("--fallback", action="store_true",
                     help="also time the chunked matmul under ~dead (one iteration per level)")
+    ap.add_argument("--compact", action="store_true",
+                    help="after the last level: compact the shard, against the torch route")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("delete_bench needs the GPU: nothing here is measured without one")
@@ -186,6 +202,104 @@ def main() -> None:
                   zero_overhead_within_spread=bool(over <= spread),
                   zero_vs_no_delete_ms=round(med["zero"] - plain["search_a"], 3),
                   zero_beats_mask=bool(med["zero"] < med["mask"])))
+    if a.compact and shard.n_dead:
+        compact_section(shard, a, q, k, run, emit, base)
+
+
+def compact_torch(rows: torch.Tensor, dead: torch.Tensor, count: int, c, windows) -> None:
+    """The plan of a compaction executed on ``rows`` with torch alone."""
+    from codename_symbiont_amd.index.shard import _unpack_bits
+
+    live = ~_unpack_bits(dead)[:count]
+    for t0, t1, _mode in windows:
+        d0, d1 = int(c[t0]), int(c[t1])
+        if d1 == d0:
+            continue
+        s0, s1 = t0 * 64, min(t1 * 64, count)
+        idx = torch.nonzero(live[s0:s1]).flatten() + s0
+        rows[d0:d1].copy_(rows.index_select(0, idx))
+
+
+def compact_section(shard, a, q, k, run, emit, base) -> None:
+    import numpy as np
+
+    from codename_symbiont_amd.index.shard import (COMPACT_STAGE_BYTES, STREAM_SUB, TILE_ROWS,
+                                                   HbmIndexShard, compact_plan)
+
+    old, n_dead = shard.count, shard.n_dead
+    info = dict(base, dead=n_dead, dead_share=round(n_dead / old, 6))
+    shard.delete_route = shard.DELETE_ROUTE_DEFAULT[a.dtype]
+    run({"tombstoned": lambda: shard.search(q, k)}, dict(info, delete_route=shard.delete_route))
+    row_bytes = shard.dim * shard.rows.element_size()
+    stage_rows = max(TILE_ROWS, COMPACT_STAGE_BYTES // row_bytes // TILE_ROWS * TILE_ROWS)
+    alt = None
+    try:
+        alt = shard.rows.clone()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        c, windows = compact_plan(shard._dead_host, old, stage_rows)
+        t1 = time.perf_counter()
+        compact_torch(alt, shard.dead, old, c, windows)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        b = int(np.flatnonzero(shard._dead_host)[0])
+        first = 8 * b + int(np.flatnonzero(np.unpackbits(shard._dead_host[b:b + 1],
+                                                         bitorder="little"))[0])
+        moved_bytes = (old - first) * row_bytes
+        emit(dict(info, variant="compact_torch", ms=round((t2 - t0) * 1e3, 3),
+                  plan_ms=round((t1 - t0) * 1e3, 3), windows=len(windows),
+                  direct=sum(m == "direct" for _, _, m in windows),
+                  gbps=round(moved_bytes / (t2 - t0) / 1e9, 1)))
+    except torch.OutOfMemoryError:
+        alt = None
+        emit(dict(info, variant="compact_torch", skipped="a second row slab does not fit"))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    shard.compact()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    lc = shard.last_compact
+    live = shard.count
+    r0 = lc["first_row"] // STREAM_SUB * STREAM_SUB
+    t0 = time.perf_counter()
+    if shard.prune_on or shard.mx4_on:
+        for s in range(r0, old, 1 << 18):
+            shard._image_rows(s, min(old, s + (1 << 18)) - s)
+    torch.cuda.synchronize()
+    reimage = time.perf_counter() - t0
+    equal = None
+    if alt is not None:
+        equal = all(torch.equal(alt[s:min(live, s + (1 << 22))],
+                                shard.rows[s:min(live, s + (1 << 22))])
+                    for s in range(0, live, 1 << 22))
+    del alt
+    all_bytes = (old - lc["first_row"]) * sum(
+        t.shape[1] * t.element_size() for t in (shard.rows, shard.rows8) if t is not None)
+    emit(dict(info, variant="compact", ms=round(dt * 1e3, 3), reimage_ms=round(reimage * 1e3, 3),
+              rows_equal=equal, **lc,
+              gbps=round(all_bytes / max(dt - reimage, 1e-9) / 1e9, 1)))
+    info = dict(base, dead=0, dead_share=0.0, rows=live, compacted_from=old)
+    variants = {"compacted": lambda: shard.search(q, k)}
+    try:
+        fresh = HbmIndexShard(shard.dim, live, device=shard.device, dtype=shard.dtype,
+                              prune=shard.prune)
+        fresh._reserve(live)
+        fresh.rows[:live].copy_(shard.rows[:live])
+        fresh.rows_written(0, live)
+        fresh.publish()
+        variants["fresh"] = lambda: fresh.search(q, k)
+    except torch.OutOfMemoryError:
+        fresh = None
+        emit(dict(info, variant="fresh", skipped="a second shard does not fit"))
+    med, times = run(variants, info)
+    if "fresh" in med:
+        s, r = shard.search(q, k)
+        fs, fr = fresh.search(q, k)
+        emit(dict(info, variant="compact_summary",
+                  compacted_vs_fresh_ms=round(med["compacted"] - med["fresh"], 3),
+                  fresh_spread_ms=round(max(times["fresh"]) - min(times["fresh"]), 3),
+                  rows_equal_fresh=rows_equal_outside_ties(s, r, fs, fr, 2e-3),
+                  max_abs_vs_fresh=float((s - fs).abs().max())))
 
 
 if __name__ == "__main__":

@@ -159,6 +159,24 @@ class PayloadStore:
         self.dirty = {r for r in self.dirty if r < n}
         self.n = n
 
+    def remap(self, new_row_of, n: int) -> None:
+        """Renumber the rows (a compaction): ``new_row_of`` maps an int64 array of old rows to
+        their new rows, ``n`` is the new row count.  Point ids and payloads follow their rows;
+        the value index is dropped (the next filter rebuilds it, rows_with) and ``dirty`` is
+        emptied: the caller makes the next snapshot a full one."""
+        def moved(d: dict) -> dict:
+            if not d:
+                return {}
+            old = np.fromiter(d.keys(), dtype=np.int64, count=len(d))
+            return dict(zip(new_row_of(old).tolist(), d.values()))
+
+        self.point_ids = moved(self.point_ids)
+        self.fields = moved(self.fields)
+        self.id_to_row = {pid: r for r, pid in self.point_ids.items()}
+        self._by_value = {}
+        self.dirty = set()
+        self.n = int(n)
+
 
 FP8_SCALE = 256.0  # == ops.kernels.FP8_SCALE (kept import-free for CPU-only users)
 
@@ -271,6 +289,78 @@ class RowMask:
     def count(self) -> int:
         """Allowed rows (reads the device: diagnostics and tests)."""
         return int(_unpack_bits(self.bits).sum())
+
+
+COMPACT_STAGE_BYTES = 256 << 20   # default staging budget of HbmIndexShard.compact
+
+
+def _dead_bytes(dead_host, count: int) -> np.ndarray:
+    """The packed bitmap over the whole tiles of rows [0, count), bits at or past ``count`` (and
+    bytes the input does not hold) clear; a copy."""
+    n_tiles = (count + TILE_ROWS - 1) // TILE_ROWS
+    h = np.zeros(n_tiles * 8, dtype=np.uint8)
+    if dead_host is not None:
+        m = min(len(dead_host), (count + 7) // 8)
+        h[:m] = np.asarray(dead_host[:m], dtype=np.uint8)
+        if count % 8:
+            h[count // 8] &= (1 << (count % 8)) - 1
+    return h
+
+
+def compact_plan(dead_host, count: int, stage_rows: int):
+    """How a compaction moves the live rows of a slab down over the dead ones, in place.
+
+    ``dead_host``: the packed tombstone bitmap (bit r % 8 of byte r // 8); rows at or past
+    ``count`` are not live.  Returns ``(c, windows)``: ``c`` (int64 [n_tiles + 1]) is the
+    exclusive prefix over 64-row tiles of the live rows per tile -- c[t] is the new row of tile
+    t's first live row, c[n_tiles] the live count -- and ``windows`` a list of ``(t0, t1, mode)``
+    over source tiles that tiles [tile of the first dead row, n_tiles) exactly (empty without a
+    dead row: rows below the first dead row never move).  Each window is one kernel launch
+    (index_compact.hip), run in order on one stream; with t1* the largest tile such that
+    c[t1*] <= 64 t0, and stage_tiles = stage_rows // 64:
+
+    * ``"direct"`` when t1* - t0 >= stage_tiles, the window [t0, t1*): every destination row
+      lies below every source row of the window, so the launch's workgroups move rows straight
+      into place in any order;
+    * ``"staged"`` otherwise, the window [t0, min(n_tiles, t0 + stage_tiles)): its live rows are
+      gathered into a staging buffer of ``stage_rows`` rows, and one contiguous copy behind the
+      gather writes them to rows [c[t0], c[t1]).
+
+    A window's destinations end at c[t1] <= 64 t1, below every later window's sources, so
+    stream order between windows is the only synchronisation."""
+    count = int(count)
+    stage_tiles = max(1, int(stage_rows) // TILE_ROWS)
+    n_tiles = (count + TILE_ROWS - 1) // TILE_ROWS
+    c = np.zeros(n_tiles + 1, dtype=np.int64)
+    if n_tiles == 0:
+        return c, []
+    dead_t = _POPCOUNT8[_dead_bytes(dead_host, count)].reshape(n_tiles, 8).sum(1)
+    rows_t = np.full(n_tiles, TILE_ROWS, dtype=np.int64)
+    rows_t[-1] = count - TILE_ROWS * (n_tiles - 1)
+    np.cumsum(rows_t - dead_t, out=c[1:])
+    holed = np.flatnonzero(dead_t)
+    windows = []
+    t0 = int(holed[0]) if holed.size else n_tiles
+    while t0 < n_tiles:
+        t1 = int(np.searchsorted(c, TILE_ROWS * t0, side="right")) - 1
+        mode = "direct"
+        if t1 - t0 < stage_tiles:
+            t1, mode = min(n_tiles, t0 + stage_tiles), "staged"
+        windows.append((t0, t1, mode))
+        t0 = t1
+    return c, windows
+
+
+def compact_new_rows(dead_host, c, rows) -> np.ndarray:
+    """New row numbers of the LIVE rows ``rows`` (int array) under the plan's prefix ``c``:
+    c[tile] plus the live rows of the tile below the row."""
+    r = np.asarray(rows, dtype=np.int64)
+    h = _dead_bytes(dead_host, TILE_ROWS * (len(c) - 1))
+    t, b = r >> 6, r & 63
+    below = (np.arange(8, dtype=np.int64)[None, :] * 8)       # first bit of each byte
+    nb = np.clip(b[:, None] - below, 0, 8)                    # bits of each byte below the row
+    by = h.reshape(-1, 8)[t] & ((1 << nb) - 1).astype(np.uint8)
+    return np.asarray(c, dtype=np.int64)[t] + b - _POPCOUNT8[by].sum(1)
 
 
 class HbmIndexShard:
@@ -443,6 +533,9 @@ class HbmIndexShard:
         self._live_mask = None
         self._live_key = None
         self._zero_hits = None
+        # compactions that moved rows (compact): row numbers handed out before one are stale
+        self.compact_gen = 0
+        self.last_compact = None
 
     # ------------------------------------------------------------------ pruning images
     def _stream_rec(self, form: int) -> int:
@@ -1021,7 +1114,8 @@ class HbmIndexShard:
         row scores exactly 0 in every scan and image (the quantisers guard amax > 0) and the
         tracked bounds only grow, so every unmasked route stays exact over the PHYSICAL rows;
         ``search`` then checks the returned ids against ``dead`` (_search_tombstoned).  The row's
-        point id and payload go; the slot is never reused and capacity is not reclaimed."""
+        point id and payload go; the slot is never reused, and capacity comes back only through
+        ``compact``."""
         if isinstance(rows, torch.Tensor):
             rows = rows.flatten().cpu().numpy()
         elif not isinstance(rows, np.ndarray):
@@ -1071,6 +1165,92 @@ class HbmIndexShard:
         the number of points deleted.  A later upsert of a deleted id appends a new row."""
         id_to_row = self.payloads.id_to_row
         return self.delete_rows([id_to_row[p] for p in point_ids if p in id_to_row])
+
+    def compact(self, stage_bytes: int = COMPACT_STAGE_BYTES) -> int:
+        """Reclaim the tombstoned rows: the live rows move down over them, in place and in order,
+        and ``count`` drops to the live count.  Returns the rows reclaimed; without a dead row
+        it returns 0 and changes nothing.
+
+        The move follows ``compact_plan`` over the ``dead`` bitmap: a few windows, each one
+        launch of compact_rows (index_compact.hip) that either writes rows straight into place
+        or gathers them into a staging buffer of ``stage_bytes`` (allocated for this call, split
+        by the row bytes of the slabs, at least one tile) that one copy then lays down.  A CPU
+        shard runs the same plan with torch indexing.  The freed tail is zeroed (the slab's
+        invariant: unwritten rows are zero), the pruning images of every sub-tile from the
+        first moved row on are re-quantised from the rows (they are per sub-tile and
+        fragment-major: not movable), the tracked bounds and the image's form stay (a bound over
+        a superset of the rows is a bound), and the payload store is renumbered.
+
+        Every row at or above the first dead one changes its number: the delete generation is
+        bumped, so RowMasks made before are refused, ``compact_gen`` counts the compactions, and
+        the next snapshot is a full one.  Searches afterwards take the unmasked route as on a
+        shard that never deleted.  The caller orders this against running searches, as for any
+        write."""
+        if self.n_dead == 0:
+            return 0
+        old_count, h = self.count, self._dead_host
+        gpu = self.device.type == "cuda"
+        slabs = [self.rows] + ([self.rows8] if self.rows8 is not None else [])
+        row_bytes = sum(t.shape[1] * t.element_size() for t in slabs)
+        stage_rows = max(TILE_ROWS, int(stage_bytes) // row_bytes // TILE_ROWS * TILE_ROWS)
+        c, windows = compact_plan(h, old_count, stage_rows)
+        live = int(c[-1])
+        b = int(np.flatnonzero(h)[0])                      # the byte of the first dead row
+        first = 8 * b + (int(h[b]) & -int(h[b])).bit_length() - 1
+        stage_rows = min(stage_rows, max((int(c[t1] - c[t0]) for t0, t1, m in windows
+                                          if m == "staged"), default=0))
+        if gpu:
+            from ..ops import kernels as K
+
+            c_dev = torch.from_numpy(c.astype(np.int32)).to(self.device)
+            dead_w = self.dead.view(torch.int64)
+            stages = [torch.empty(stage_rows, t.shape[1], dtype=t.dtype, device=self.device)
+                      if stage_rows else None for t in slabs]
+            stages += [None] * (2 - len(stages))
+        else:
+            bits = np.unpackbits(_dead_bytes(h, old_count), bitorder="little")[:old_count]
+        for t0, t1, mode in windows:
+            d0, d1 = int(c[t0]), int(c[t1])
+            if d1 == d0:
+                continue
+            if gpu:
+                staged = mode == "staged"
+                K.compact_rows(dead_w, c_dev, t0, t1, old_count, self.rows,
+                               stages[0] if staged else None, self.rows8,
+                               stages[1] if staged else None, n_rows=d1 - d0)
+                if staged:
+                    for t, g in zip(slabs, stages):
+                        t[d0:d1].copy_(g[:d1 - d0])
+            else:
+                s0, s1 = t0 * TILE_ROWS, min(t1 * TILE_ROWS, old_count)
+                src = torch.from_numpy(s0 + np.flatnonzero(bits[s0:s1] == 0))
+                for t in slabs:
+                    t[d0:d1] = t[src]
+        for t in slabs:
+            t[live:old_count].zero_()
+        # the images of every sub-tile from the one holding the first moved row, up to the old
+        # count (the zeroed tail quantises to zero images); in the image's current form
+        if self.prune_on or self.mx4_on:
+            r0 = first // STREAM_SUB * STREAM_SUB
+            chunk = 1 << 18
+            for s in range(r0, old_count, chunk):
+                self._image_rows(s, min(old_count, s + chunk) - s)
+        self.payloads.remap(lambda rows: compact_new_rows(h, c, rows), live)
+        self.dead.zero_()
+        h[:] = 0
+        self.n_dead = 0
+        self.count = self.visible = live
+        self.dead_gen += 1
+        self._live_mask = self._live_key = None
+        self.last_dead_hits = None
+        self._persisted, self._dirty, self._persist_key = 0, set(), None
+        self.compact_gen += 1
+        self.last_compact = {
+            "reclaimed": old_count - live, "first_row": first,
+            "direct_windows": sum(m == "direct" for _, _, m in windows),
+            "staged_windows": sum(m == "staged" for _, _, m in windows),
+            "rows_moved": live - first}
+        return old_count - live
 
     def _live(self) -> RowMask:
         """The RowMask of the rows that are not tombstoned: ~dead over the packed words (no bool

@@ -201,6 +201,51 @@ class VectorStore:
                 self._start(self._cut_locked(), background=True)
             return n
 
+    @property
+    def compact_gen(self) -> int:
+        """Compactions that renumbered rows so far (see ``compact``)."""
+        return self.shard.compact_gen
+
+    def compact(self, snapshot: bool = True) -> int:
+        """Reclaim the rows of deleted points (HbmIndexShard.compact): the live rows move down
+        over them in place, ``count`` drops to ``live_count`` and the freed capacity takes new
+        upserts.  Returns the rows reclaimed (0: nothing was deleted, nothing changes).
+
+        ROW NUMBERS CHANGE: the rows a search returned are valid for ``lookup`` /
+        ``result_fragments`` only until the next compaction; ``compact_gen`` tells (read it
+        before the search and after the lookups).  That is why nothing here compacts by itself.
+
+        No log record is written: the log holds upserts and deletes by point id, so a crash
+        before the next snapshot commits restores the same points, merely uncompacted.  With a
+        snapshot directory and ``snapshot`` set, a full snapshot is cut and written before this
+        returns (the next one is full either way: the incremental record speaks of old rows)."""
+        if self.group is not None:
+            raise ValueError("compact is single-shard for now: this store writes a multi-GPU group")
+        self.flush()
+        with self._lock:
+            self.flush()     # (a snapshot an upsert started meanwhile)
+            if self._streams is not None:
+                self._rw.acquire_write()
+                try:
+                    # the moves must not land under a pipelined search's pre-pass or scan
+                    cur = torch.cuda.current_stream(self.shard.device)
+                    cur.wait_stream(self._streams[0])
+                    cur.wait_stream(self._streams[1])
+                    n = self.shard.compact()
+                finally:
+                    self._rw.release_write()
+            else:
+                n = self.shard.compact()
+            if n == 0:
+                return 0
+            if self.shard.device.type == "cuda":
+                torch.cuda.synchronize(self.shard.device)
+            self._frag.clear()       # cached by row
+            self._masks.clear()
+            job = self._cut_locked() if self.dir and snapshot else None
+        self._start(job, background=False)
+        return n
+
     def _upsert_nolog(self, point_ids, vecs, payloads):
         t = torch.as_tensor(np.ascontiguousarray(vecs, dtype=np.float32))
         if self._streams is not None:

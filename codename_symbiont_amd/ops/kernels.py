@@ -471,3 +471,62 @@ def results_dead(ids: torch.Tensor, dead_words: torch.Tensor, hits: torch.Tensor
         raise ValueError("results_dead: ids, bitmap and flag on different devices")
     hip().results_dead(_ptr(ids), ids.numel(), _ptr(dead_words), dead_words.numel(), _ptr(hits),
                        stream_handle(ids.device))
+
+
+def compact_rows(dead_words: torch.Tensor, tile_dst: torch.Tensor, t0: int, t1: int, n_valid: int,
+                 slab: torch.Tensor, stage: torch.Tensor | None = None,
+                 slab2: torch.Tensor | None = None, stage2: torch.Tensor | None = None,
+                 n_rows: int = 0) -> None:
+    """Move the live rows of source tiles [t0, t1) (64 rows each) of one compaction window
+    (index_compact.hip; the windows come from index.shard.compact_plan).  ``dead_words``: the
+    tombstone bitmap (int64, bit r % 64 of word r // 64); ``tile_dst``: int32 [>= n_tiles + 1],
+    tile_dst[t] = the new row of tile t's first live row; rows at or past ``n_valid`` are not live.
+
+    ``stage`` None = a direct window: the rows go to ``slab[tile_dst[t] + rank]`` (the plan
+    guarantees every destination lies below the window).  Otherwise a staged window: they are
+    gathered into ``stage[tile_dst[t] - tile_dst[t0] + rank]`` and the caller copies
+    ``stage[:n_rows]`` to ``slab[tile_dst[t0]:tile_dst[t1]]`` behind this call; ``n_rows`` is that
+    row count from the host's plan and must fit the staging buffer.  ``slab2`` / ``stage2``: a
+    second slab moved the same way in the same launch (a shard's e4m3 prefilter image).  Slabs are
+    [>= n_valid, D] of 1- or 2-byte elements, D a multiple of 8."""
+    _chk(dead_words, torch.int64, "dead_words", 1)
+    _chk(tile_dst, torch.int32, "tile_dst", 1)
+    t0, t1, n_valid, n_rows = int(t0), int(t1), int(n_valid), int(n_rows)
+    dev, D = slab.device, slab.shape[-1]
+    n_tiles = (n_valid + 63) // 64
+    if n_valid <= 0 or not 0 <= t0 < t1 <= n_tiles:
+        raise ValueError(f"compact_rows: window [{t0}, {t1}) outside the {n_tiles} tiles of "
+                         f"{n_valid} rows")
+    if dead_words.numel() < n_tiles or tile_dst.numel() < n_tiles + 1:
+        raise ValueError(f"compact_rows: {dead_words.numel()} bitmap words / {tile_dst.numel()} "
+                         f"tile offsets do not cover {n_tiles} tiles")
+    if dead_words.device != dev or tile_dst.device != dev:
+        raise ValueError("compact_rows: bitmap, tile offsets and slab on different devices")
+    if (stage is None) != (stage2 is None) and slab2 is not None:
+        raise ValueError("compact_rows: both slabs are staged or neither")
+    if slab2 is None and stage2 is not None:
+        raise ValueError("compact_rows: stage2 without slab2")
+    for name, t, need in (("slab", slab, n_valid), ("slab2", slab2, n_valid),
+                          ("stage", stage, n_rows), ("stage2", stage2, n_rows)):
+        if t is None:
+            continue
+        if t.element_size() not in (1, 2):
+            raise TypeError(f"compact_rows: {name} must hold 1- or 2-byte elements, got {t.dtype}")
+        _chk(t, t.dtype, name, 2)
+        if t.shape[1] != D or D % 8 or t.shape[0] < need or t.device != dev:
+            raise ValueError(f"compact_rows: {name} {tuple(t.shape)} does not hold {need} rows "
+                             f"of width {D} (a multiple of 8) on {dev}")
+        if t.data_ptr() % 16:
+            raise ValueError(f"compact_rows: {name} is not 16-byte aligned")
+    for s, g, name in ((slab, stage, "stage"), (slab2, stage2, "stage2")):
+        if g is not None and g.dtype != s.dtype:
+            raise TypeError(f"compact_rows: {name} is {g.dtype}, its slab {s.dtype}")
+    if stage is not None and n_rows < 0:
+        raise ValueError("compact_rows: n_rows < 0")
+    cap = 0 if stage is None else stage.shape[0]
+    if stage2 is not None:
+        cap = min(cap, stage2.shape[0])
+    hip().compact_rows(_ptr(dead_words), _ptr(tile_dst), t0, t1, n_valid, _ptr(slab),
+                       slab.element_size(), _ptr(stage), _ptr(slab2),
+                       0 if slab2 is None else slab2.element_size(), _ptr(stage2), D, n_rows, cap,
+                       stream_handle(dev))

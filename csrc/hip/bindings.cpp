@@ -104,6 +104,10 @@ int symb_tombstone_rows(const int* rows, int n, int n_valid, void* slab0, int es
                         int es1, int D, void* dead, hipStream_t st);
 int symb_results_dead(const int* ids, int n, const void* dead, int n_words, int* hits,
                       hipStream_t st);
+// in-place compaction of tombstoned rows (index_compact.hip)
+int symb_compact_rows(const void* dead, const int* tile_dst, int t0, int t1, int n_valid,
+                      void* slab0, int es0, void* stage0, void* slab1, int es1, void* stage1, int D,
+                      int n_rows, int stage_cap, hipStream_t st);
 int symb_mq_queries_per_blk(int sets, int rsplit);
 int symb_i8_queries_per_blk(int rsplit);
 int symb_index_scan_i8(const void* X8, const float* sx, int n_valid, int alloc_rows,
@@ -950,6 +954,16 @@ PYBIND11_MODULE(_hip, m) {
           "results_dead");
   }, py::arg("ids"), py::arg("n"), py::arg("dead"), py::arg("n_words"), py::arg("hits"),
      py::arg("stream"));
+  m.def("compact_rows", [](uptr dead, uptr tile_dst, int t0, int t1, int n_valid, uptr slab0,
+                           int es0, uptr stage0, uptr slab1, int es1, uptr stage1, int D,
+                           int n_rows, int stage_cap, uptr st) {
+    check(symb_compact_rows(P<void>(dead), P<const int>(tile_dst), t0, t1, n_valid, P<void>(slab0),
+                            es0, P<void>(stage0), P<void>(slab1), es1, P<void>(stage1), D, n_rows,
+                            stage_cap, S(st)),
+          "compact_rows");
+  }, py::arg("dead"), py::arg("tile_dst"), py::arg("t0"), py::arg("t1"), py::arg("n_valid"),
+     py::arg("slab0"), py::arg("es0"), py::arg("stage0"), py::arg("slab1"), py::arg("es1"),
+     py::arg("stage1"), py::arg("D"), py::arg("n_rows"), py::arg("stage_cap"), py::arg("stream"));
   m.def("topk_merge", [](uptr cand_s, uptr cand_i, int NQ, int n_cand, int kmax, int k,
                          uptr out_s, uptr out_i, int64_t id_offset, uptr out_id64, uptr st,
                          uptr gate) {
