@@ -21,10 +21,12 @@ Every line carries ``last_dead_hits`` (must be 0: each query keeps k live rows s
 ``rows_equal_mask`` (the result against the masked scan's: same rows outside runs of equal scores)
 and ``max_abs_vs_mask``; the ``delete`` lines carry the cost of the delete itself per 1k rows.
 
-k > 32 (bf16 shards: the masked emitting scan, index_mq_filter.hip, is the masked route): the
-``mask`` line also carries ``overflow`` (its candidate-overflow flag: 1 = it fell back to the
-masked matmul) and ``max_candidates``; --fallback adds ``matmul_mask``, one iteration of the
-chunked matmul under ~dead, the route of such a search before the masked emitting scan.
+k > 32 (the masked emitting scan is the masked route: index_mq_filter.hip on bf16 shards,
+index_emit_fp8.hip on fp8 shards of FP8_LARGE_K_MIN_ROWS rows or more, where it is the unmasked
+route too, under an all-ones mask): the ``mask`` line, and on fp8 every line but ``zero``, also
+carries ``overflow`` (the candidate-overflow flag: 1 = the search fell back to the masked matmul)
+and ``max_candidates``; --fallback adds ``matmul_mask``, one iteration of the chunked matmul
+under ~dead, the route of such a search before the masked emitting scan.
 
 --compact adds, after the last level's lines (nothing above changes), the in-place compaction
 (HbmIndexShard.compact, csrc/hip/index_compact.hip) of what the levels left:
@@ -145,7 +147,9 @@ def main() -> None:
             res[v] = fn()
             hits[v] = 0 if shard.last_dead_hits is None else int(shard.last_dead_hits)
             last = shard._filter_large_k_last
-            if v == "mask" and last is not None:
+            # (not "zero": its gated fallback runs last, and behind a closed gate it leaves the
+            # counts unwritten)
+            if v != "zero" and last is not None:
                 large[v] = {"overflow": int(last[1]), "max_candidates": int(last[0].max())}
         torch.cuda.synchronize()
         times = {v: [] for v in variants}

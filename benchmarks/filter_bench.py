@@ -14,11 +14,14 @@ Per mask, in alternated rounds on the same shard (one JSON line per mask and var
   matmul_mask      (--fallback) the chunked matmul under the mask, the route of every shard the
                    masked scan does not serve and of fp8 shards before it did: one iteration
 
-k > 32 (the masked emitting scan, index_mq_filter.hip, on bf16 shards): the list scans stop at
-kmax = 32, so the variants are ``filtered`` (shard.search(q, k, allow=mask)) and ``search`` (the
-unfiltered top-k), plus matmul_mask with --fallback; every ``filtered`` line carries ``overflow``
-(the route's candidate-overflow flag: 1 means the search fell back to the masked matmul) and
-``max_candidates`` (the most candidates one query emitted).
+k > 32 (the masked emitting scan: index_mq_filter.hip on bf16 shards, index_emit_fp8.hip on fp8
+shards of FP8_LARGE_K_MIN_ROWS rows or more): the list scans stop at kmax = 32, so the variants
+are ``filtered`` (shard.search(q, k, allow=mask)), ``search`` (the unfiltered top-k; on an fp8
+shard the same route under an all-ones mask) and ``search_k32`` (the unfiltered list-scan search
+at k = 32, as context), plus matmul_mask with --fallback; every line of a search that took the
+emitting route carries ``overflow`` (the route's candidate-overflow flag: 1 means the search fell
+back to the masked matmul), ``max_candidates`` (the most candidates one query emitted) and
+``cap`` (LARGE_K_CAP).
 
 --dtype fp8: the shard holds e4m3 rows, gather_scan is the fp8 list scan over the index_select-ed
 bytes, and every record carries "dtype": "fp8", rows_equal_gather (the masked scan's rows against
@@ -195,18 +198,21 @@ def main() -> None:
             variants["gather_scan"] = gather
         if large_k:
             variants = {"filtered": lambda: shard.search(q, k, allow=mask),
-                        "search": lambda: shard.search(q, k)}
+                        "search": lambda: shard.search(q, k),
+                        "search_k32": lambda: shard.search(q, 32)}
         # results first (also the warm-up of every shape): seed on == seed off == gather
-        shard._filter_large_k_last = None
-        res = {v: fn() for v, fn in variants.items()}
-        torch.cuda.synchronize()
-        same_seed, per_variant = None, {}
-        if large_k:
-            last = getattr(shard, "_filter_large_k_last", None)
-            if last is not None:
-                per_variant["filtered"] = {"overflow": int(last[1]),
-                                           "max_candidates": int(last[0].max())}
-        else:
+        res, same_seed, per_variant = {}, None, {}
+        for v, fn in variants.items():
+            # (an fp8 shard's unfiltered search at this k is the same route under an all-ones
+            # mask and leaves its own counts: read them per variant)
+            shard._filter_large_k_last = None
+            res[v] = fn()
+            torch.cuda.synchronize()
+            last = shard._filter_large_k_last
+            if large_k and last is not None:
+                per_variant[v] = {"overflow": int(last[1]), "max_candidates": int(last[0].max()),
+                                  "cap": int(shard.LARGE_K_CAP)}
+        if not large_k:
             same_seed = bool(torch.equal(res["filtered_seed"][0], res["filtered_noseed"][0])
                              and torch.equal(res["filtered_seed"][1], res["filtered_noseed"][1]))
         same_gather = None

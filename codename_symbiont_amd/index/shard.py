@@ -222,6 +222,7 @@ I8_RING_DIMS = (768,)
 FILTER_DIMS = (384, 768, 1024)          # ... the masked list scan (index_filter.hip)
 FILTER_FP8_DIMS = (256, 384, 512, 768, 1024)   # ... its e4m3 form (index_filter_fp8.hip)
 FILTER_LARGE_K_DIMS = (384, 768, 1024)  # ... the masked emitting scan (index_mq_filter.hip)
+FILTER_LARGE_K_FP8_DIMS = FILTER_FP8_DIMS      # ... its e4m3 form (index_emit_fp8.hip)
 
 
 def filter_large_k_threshold(cand_s: torch.Tensor, k: int, margin: float) -> torch.Tensor:
@@ -235,6 +236,16 @@ def filter_large_k_threshold(cand_s: torch.Tensor, k: int, margin: float) -> tor
     s = torch.where(torch.isfinite(cand_s), cand_s, torch.full_like(cand_s, -math.inf))
     kth = torch.topk(s, k, dim=1).values[:, k - 1]
     return (kth - margin).float().contiguous()
+
+
+def filter_large_k_threshold_ulp(cand_s: torch.Tensor, k: int) -> torch.Tensor:
+    """``filter_large_k_threshold`` for a seed pass and an emitting scan that score a row bit for
+    bit alike (the fp8 pair, which shares one MFMA chain): the k-th largest FINITE entry moved one
+    ulp towards -inf, so the emitting scan's strict ``score > T`` keeps every row scoring at
+    least that entry; -inf where fewer than k entries are finite.  NaN entries (a gated-off seed
+    pass leaves its workspace unwritten) count as missing, and the result is never NaN."""
+    kth = filter_large_k_threshold(cand_s, k, 0.0)
+    return torch.nextafter(kth, torch.full_like(kth, -math.inf)).contiguous()
 
 
 def _pack_bits(allow: torch.Tensor, n_words: int) -> torch.Tensor:
@@ -532,6 +543,7 @@ class HbmIndexShard:
         self.last_dead_hits = None   # device int32 [1]: dead ids the last search's route returned
         self._live_mask = None
         self._live_key = None
+        self._all_rows_mask = None   # _all_rows: the all-ones RowMask of the rows visible then
         self._zero_hits = None
         # compactions that moved rows (compact): row numbers handed out before one are stale
         self.compact_gen = 0
@@ -1271,6 +1283,27 @@ class HbmIndexShard:
             self._live_key = key
         return self._live_mask
 
+    def _all_rows(self) -> RowMask:
+        """The RowMask that allows every visible row, with its tile list: what the unmasked fp8
+        search at 32 < k <= 128 runs the masked emitting scan under (on fp8 a masked and an
+        unmasked search are the same list scan).  Built once per number of visible rows.
+        Internal: it ignores tombstones and is never checked against ``dead_gen``."""
+        v = self.visible
+        cached = self._all_rows_mask
+        if cached is None or cached.visible != v:
+            nw = max(1, (v + TILE_ROWS - 1) // TILE_ROWS)
+            words = torch.full((nw,), -1, dtype=torch.int64, device=self.device)
+            if v < nw * 64:      # bits at or past ``visible`` are clear in a RowMask
+                words[v // 64:v // 64 + 1].bitwise_and_((1 << (v % 64)) - 1)
+            tiles = n_live = None
+            if self.device.type == "cuda":
+                from ..ops.kernels import filter_tiles
+
+                tiles, n_live = filter_tiles(words, v)
+            cached = self._all_rows_mask = RowMask(words.view(torch.uint8), v, tiles, n_live,
+                                                   self.dead_gen)
+        return cached
+
     def fill_random(self, n: int, seed: int = 0, chunk: int = 1 << 20) -> None:
         """Synthetic unit rows straight into HBM (benchmark corpus; no payloads)."""
         g = torch.Generator(device=self.device)
@@ -1293,7 +1326,12 @@ class HbmIndexShard:
 
         On a bf16 GPU shard of width 384 / 768 / 1024 both run on the HIP scans up to k = 128
         (k <= 32: the masked list scan; above: the masked emitting scan); beyond that, and on
-        shards those scans do not serve, they take the chunked matmul under the mask.
+        shards those scans do not serve, they take the chunked matmul under the mask.  A GPU fp8
+        shard (256 / 384 / 512 / 768 / 1024) has the e4m3 forms of both: the list scan at
+        k <= 32, and at 32 < k <= 128, from FP8_LARGE_K_MIN_ROWS visible rows on, the emitting
+        e4m3 scan -- unmasked searches too, under an all-ones mask.  Every HIP route of an fp8
+        shard scores e4m3(q) . e4m3(x); its matmul (smaller shards at k > 32, k > 128) scores
+        float(q) . decode(x).
 
         Returns (scores f32 [NQ, k], rows int32 [NQ, k]); missing slots are (-inf, -1)."""
         if allow is not None:
@@ -1320,6 +1358,10 @@ class HbmIndexShard:
             out = self._search_large_k(q_unit, k, n_cus)
             if out is not None:
                 return out
+            if k > 32 and self.dtype == "fp8" and self._filter_large_k_serves(k):
+                # an fp8 shard of FP8_LARGE_K_MIN_ROWS rows or more: the emitting e4m3 scan
+                # under the all-ones mask (masked and unmasked are one list scan on fp8)
+                return self._search_filtered_large_k(q_unit, k, self._all_rows(), n_cus)
             if k > 32:
                 return self._search_matmul(q_unit, k)
         if self.prune and k <= 16 and NQ >= self.prune_min_nq and self._seed_rows(self.visible, k):
@@ -1350,7 +1392,10 @@ class HbmIndexShard:
         where(hit, fallback, route).  No hit is the only outcome while every query has at least
         k live rows scoring above 0, so each route keeps its own speed after deletes.
         ``delete_route = "mask"`` goes straight to the masked scan; CPU shards, k > 128, fp8
-        shards at k > 32 and widths no masked scan serves take the masked matmul."""
+        shards below FP8_LARGE_K_MIN_ROWS rows at k > 32 and widths no masked scan serves take
+        the masked matmul.  On a larger fp8 shard at 32 < k <= 128 the route under "zero" is the
+        emitting e4m3 scan under the all-ones mask and the fallback the same scan under the live
+        mask."""
         NQ, k = q_unit.shape[0], int(k)
         if NQ == 0 or k <= 0:
             return self._search_route(q_unit, k, n_cus)
@@ -1477,10 +1522,16 @@ class HbmIndexShard:
                 or (self.dtype == "fp8" and self.dim in FILTER_FP8_DIMS))
 
     def _filter_large_k_serves(self, k: int) -> bool:
-        """The masked emitting scan serves a search at this k: a bf16 shard on a GPU at a width
-        in FILTER_LARGE_K_DIMS with the emitting scan on, 32 < k <= K_MAX_HIP."""
-        return (self.device.type == "cuda" and self.dtype == "bf16" and bool(self.scan_mq)
-                and self.dim in FILTER_LARGE_K_DIMS and 32 < k <= self.K_MAX_HIP)
+        """The masked emitting scan serves a search at this k, 32 < k <= K_MAX_HIP: a bf16 shard
+        on a GPU at a width in FILTER_LARGE_K_DIMS with the emitting scan on, or an fp8 shard on
+        a GPU at a width in FILTER_LARGE_K_FP8_DIMS with FP8_LARGE_K_MIN_ROWS visible rows or
+        more (below them the matmul costs milliseconds)."""
+        if self.device.type != "cuda" or not 32 < k <= self.K_MAX_HIP:
+            return False
+        if self.dtype == "fp8":
+            return (self.dim in FILTER_LARGE_K_FP8_DIMS
+                    and self.visible >= self.FP8_LARGE_K_MIN_ROWS)
+        return (self.dtype == "bf16" and bool(self.scan_mq) and self.dim in FILTER_LARGE_K_DIMS)
 
     def _mask_tiles_wanted(self) -> bool:
         """Some masked scan of this shard walks a RowMask's live-tile list."""
@@ -1489,10 +1540,11 @@ class HbmIndexShard:
     def _search_masked(self, q_unit, k: int, n_cus, allow):
         """``search`` under a row mask, exact over the allowed rows.  A GPU shard at k <= 32 takes
         the masked list scan of its row format (bf16 at a width in FILTER_DIMS, fp8 at one in
-        FILTER_FP8_DIMS); a bf16 GPU shard at 32 < k <= 128 and a width in FILTER_LARGE_K_DIMS the
-        masked emitting scan (_search_filtered_large_k); everything else (CPU shards, k > 128, fp8
-        shards at k > 32, other widths) the chunked matmul
-        with the score block masked.  On an fp8 shard the list scan scores e4m3(q) . e4m3(x), as
+        FILTER_FP8_DIMS); at 32 < k <= 128 a bf16 GPU shard at a width in FILTER_LARGE_K_DIMS, and
+        an fp8 one at a width in FILTER_LARGE_K_FP8_DIMS with FP8_LARGE_K_MIN_ROWS visible rows or
+        more, the masked emitting scan (_search_filtered_large_k); everything else (CPU shards,
+        k > 128, smaller fp8 shards at k > 32, other widths) the chunked matmul
+        with the score block masked.  On an fp8 shard both scans score e4m3(q) . e4m3(x), as
         the unmasked GPU search does; the matmul scores float(q) . decode(x).  The cheap routes of
         the unmasked search do not apply: their thresholds come from a sample of ALL rows, which
         is no lower bound on the k-th allowed score."""
@@ -1554,7 +1606,10 @@ class HbmIndexShard:
            as _search_large_k reads its own) and the search takes the masked matmul.
 
         ``gate`` (int32 device flag): every launch runs only if it is non-zero; at 0 the
-        overflow flag stays 0 and the outputs hold garbage the caller never selects."""
+        overflow flag stays 0 and the outputs hold garbage the caller never selects.
+
+        An fp8 shard (FILTER_LARGE_K_FP8_DIMS) runs the same three steps on its own kernels
+        (_filtered_large_k_fp8)."""
         from ..ops import kernels as K
         from ..ops._ext import hip, stream_handle
 
@@ -1568,6 +1623,9 @@ class HbmIndexShard:
         if n_cus is None:
             n_cus = self._n_cus()
         tile_slots = math.ceil(n / (TILE_ROWS * self.FILTER_MIN_TILES))
+        if self.dtype == "fp8":
+            return self._filtered_large_k_fp8(q_unit, k, mask, n, n_cus, tile_slots, gate, seed,
+                                              out_s, out_i)
         if seed:
             lists, qpb = h.topk_geometry(self.dim, 32)
             n_rblk = max(1, min(tile_slots, max(1, round(n_cus / math.ceil(NQ / qpb)))))
@@ -1614,6 +1672,62 @@ class HbmIndexShard:
         self._filter_large_k_last = (cnt, ovf)   # candidate counts / overflow flag (tests)
         if int(ovf.item()):
             return self._search_matmul(q_unit, k, mask=mask)
+        return out_s, out_i
+
+    def _filtered_large_k_fp8(self, q_unit, k: int, mask: RowMask, n: int, n_cus: int,
+                              tile_slots: int, gate, seed: bool, out_s, out_i):
+        """_search_filtered_large_k on an fp8 shard: the queries are quantised to e4m3 once; the
+        seed passes are the masked e4m3 list scan (index_filter_fp8.hip: 2 lists, 256 queries per
+        block) at the same stride and coarse stride; the emitting e4m3 scan (index_emit_fp8.hip)
+        keeps every allowed row above T.  Both kernels run one MFMA chain, so a row's raw score
+        (S^2 * cosine) is the same bits in each, and T is the k-th largest finite raw candidate
+        less one ulp, with no margin (filter_large_k_threshold_ulp).  The selected scores are
+        rescaled once at the end.  On overflow the masked matmul runs on the DECODED quantised
+        queries, so it differs from the scan by summation order only, not by the queries' e4m3
+        rounding."""
+        from ..ops import kernels as K
+        from ..ops._ext import hip, stream_handle
+
+        h, dev = hip(), self.device
+        NQ = q_unit.shape[0]
+        q8 = K.quant_fp8(q_unit, scale=FP8_SCALE)
+        n_qblk = math.ceil(NQ / 256)
+        n_rblk = max(1, min(tile_slots, max(1, round(n_cus / n_qblk))))
+        if seed:
+            cs = torch.empty(NQ, n_rblk * 2 * 32, device=dev)
+            ci = torch.empty(NQ, n_rblk * 2 * 32, dtype=torch.int32, device=dev)
+            T0 = None
+            if self.FILTER_LARGE_K_COARSE > 1 and n >= self.SEED_MIN_ROWS:
+                # the seed pass's own seed, as on bf16: a subset of its sample, so T is unchanged
+                c0 = torch.empty(NQ, n_rblk * 2 * 16, device=dev)
+                i0 = torch.empty(NQ, n_rblk * 2 * 16, dtype=torch.int32, device=dev)
+                K.index_scan_filter_fp8(self.rows, n, mask.words, mask.tiles, mask.n_live, q8, 16,
+                                        n_rblk, c0, i0, None,
+                                        self.FILTER_LARGE_K_STRIDE * self.FILTER_LARGE_K_COARSE,
+                                        self.scan_xcd, gate)
+                T0 = filter_large_k_threshold_ulp(c0, k)
+            K.index_scan_filter_fp8(self.rows, n, mask.words, mask.tiles, mask.n_live, q8, 32,
+                                    n_rblk, cs, ci, T0, self.FILTER_LARGE_K_STRIDE, self.scan_xcd,
+                                    gate)
+            T = filter_large_k_threshold_ulp(cs, k)
+        else:
+            T = torch.full((NQ,), -math.inf, device=dev)
+        cap = self.LARGE_K_CAP
+        es = torch.empty(NQ, cap, device=dev)
+        ei = torch.empty(NQ, cap, dtype=torch.int32, device=dev)
+        cnt = torch.empty(NQ, dtype=torch.int32, device=dev)
+        # this search's own overflow flag; zeroed here, so a closed gate leaves it 0
+        ovf = torch.zeros(1, dtype=torch.int32, device=dev)
+        K.index_scan_emit_fp8(self.rows, n, mask.words, mask.tiles, mask.n_live, q8, T, es, ei,
+                              cnt, cap, n_rblk, self.scan_xcd, gate)
+        h.topk_select_counted(es.data_ptr(), ei.data_ptr(), cnt.data_ptr(), cap, NQ, 128, k,
+                              out_s.data_ptr(), out_i.data_ptr(), ovf.data_ptr(),
+                              stream_handle(dev), gate=0 if gate is None else gate.data_ptr(),
+                              reset_ovf=False)
+        out_s.mul_(1.0 / (FP8_SCALE * FP8_SCALE))   # (-inf stays -inf)
+        self._filter_large_k_last = (cnt, ovf)   # candidate counts / overflow flag (tests)
+        if int(ovf.item()):
+            return self._search_matmul(K.fp8_to_float(q8, FP8_SCALE), k, mask=mask)
         return out_s, out_i
 
     def _search_filtered(self, q_unit, k: int, mask: RowMask, n_cus, gate=None):
@@ -2366,6 +2480,9 @@ class HbmIndexShard:
 
     SEED_DIV = 64            # sample = first n/64 rows (~1.6% extra scan work)
     SEED_MIN_ROWS = 1 << 20  # below this the record-breaking inserts are cheap anyway
+    # visible rows from which an fp8 shard at 32 < k <= 128 takes the emitting e4m3 scan (the gate
+    # _search_large_k applies on bf16): below it the chunked matmul costs milliseconds
+    FP8_LARGE_K_MIN_ROWS = SEED_MIN_ROWS
 
     def _seed_rows(self, n: int, k: int) -> int:
         if not self.seed_threshold or n < self.SEED_MIN_ROWS:
@@ -2428,7 +2545,9 @@ class HbmIndexShard:
         return out_s, out_i
 
     def _search_matmul(self, q_unit: torch.Tensor, k: int, chunk: int = 1 << 22, mask=None):
-        """Chunked exact fallback (CPU backend, or k > 32 on GPU).  Each chunk's fp32 score block
+        """Chunked exact fallback (CPU backend; on the GPU k > 128, k > 32 where no emitting scan
+        serves the shard -- an fp8 shard below FP8_LARGE_K_MIN_ROWS rows among them -- and a
+        large-k search whose candidates overflowed).  Each chunk's fp32 score block
         stays <= 512 MiB: one GEMM output past 2 GiB came back with its tail unwritten on the
         GPU stack (benchmarks/diag/gemm_2g.py).  ``mask`` (RowMask): disallowed rows score -inf;
         score column j of a chunk is row s + j, so the chunk takes the mask's rows [s, e)."""

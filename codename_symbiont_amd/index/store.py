@@ -372,7 +372,8 @@ class VectorStore:
         ``filter`` (index.filter.Filter): only points that pass may be returned; the search is
         exact over them, and slots past the passing points are (-inf, -1).  On a bf16 GPU shard of
         width 384 / 768 / 1024 a filtered search, and any search after a ``delete``, stays on the
-        HIP scans up to k = 128 (HbmIndexShard._search_masked / _search_tombstoned)."""
+        HIP scans up to k = 128 (HbmIndexShard._search_masked / _search_tombstoned); so does every
+        search of an fp8 GPU shard of 2^20 rows or more (k <= 32 at any size)."""
         if filter is not None and self.group is not None:
             raise ValueError("filtered search is single-shard for now: this store searches a "
                              "multi-GPU group")

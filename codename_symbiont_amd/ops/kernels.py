@@ -426,6 +426,60 @@ def index_scan_filter_fp8(rows_u8: torch.Tensor, n_valid: int, mask_words: torch
                                 _ptr(thr_init), xcd, _ptr(gate))
 
 
+def index_scan_emit_fp8(rows_u8: torch.Tensor, n_valid: int, mask_words: torch.Tensor,
+                        tiles: torch.Tensor, n_live: torch.Tensor, q_e4m3: torch.Tensor,
+                        thr: torch.Tensor, cand_s: torch.Tensor, cand_i: torch.Tensor,
+                        cand_n: torch.Tensor, cap: int, n_rblk: int, xcd: int = 1,
+                        gate: torch.Tensor | None = None, zero_cnt: bool = True) -> None:
+    """The masked emitting scan over e4m3 rows (index_emit_fp8.hip): every allowed row below
+    ``n_valid`` whose raw score (FP8_SCALE**2 * cosine, the list scan's own accumulator) lies
+    above ``thr[q]`` is appended to query q's candidates, ``cand_s`` / ``cand_i`` [NQ, cap], and
+    counted in ``cand_n`` [NQ] -- which may exceed ``cap``; nothing is written at or past it
+    (``topk_select_counted`` raises its overflow flag then).  ``tiles`` / ``n_live`` are
+    ``filter_tiles(mask_words, n_valid)``; the grid is ``n_rblk`` row slots per block of 256
+    queries, sharing the live tiles evenly.  ``zero_cnt`` False appends to ``cand_n``.  ``gate``
+    (int32 device flag): scan and zeroing run only if it is non-zero, and leave every buffer
+    untouched otherwise."""
+    if rows_u8.dtype != torch.uint8 or q_e4m3.dtype != torch.uint8:
+        # (a bf16 slab of the same width would be read as twice as many e4m3 rows)
+        raise ValueError("index_scan_emit_fp8: rows and queries are e4m3 bytes (uint8), got "
+                         f"{rows_u8.dtype} / {q_e4m3.dtype}")
+    _chk(rows_u8, torch.uint8, "rows_u8", 2)
+    _chk(q_e4m3, torch.uint8, "q_e4m3", 2)
+    _chk(mask_words, torch.int64, "mask_words", 1)
+    _chk(tiles, torch.int32, "tiles", 1)
+    _chk(n_live, torch.int32, "n_live", 1)
+    if thr is None or thr.dtype != torch.float32:
+        raise ValueError("index_scan_emit_fp8: thr is a float32 tensor, one threshold per query")
+    _chk(thr, torch.float32, "thr", 1)
+    _chk(cand_s, torch.float32, "cand_s")
+    _chk(cand_i, torch.int32, "cand_i")
+    _chk(cand_n, torch.int32, "cand_n", 1)
+    D = rows_u8.shape[1]
+    NQ = q_e4m3.shape[0]
+    n_valid, n_rblk, cap = int(n_valid), int(n_rblk), int(cap)
+    if D not in FILTER_FP8_DIMS or q_e4m3.shape[1] != D:
+        raise ValueError(f"index_scan_emit_fp8: rows must be {FILTER_FP8_DIMS} wide, queries alike")
+    if n_rblk < 1 or cap < 1 or n_valid < 0 or n_live.numel() < 1:
+        raise ValueError("index_scan_emit_fp8: n_rblk >= 1, cap >= 1, n_valid >= 0")
+    n_tiles = (n_valid + 63) // 64
+    # every tile the list can name lies inside the row slab and has a mask word
+    if n_tiles * 64 > rows_u8.shape[0] or n_tiles > mask_words.numel() or n_tiles > tiles.numel():
+        raise ValueError("index_scan_emit_fp8: rows / mask / tile list shorter than n_valid")
+    if thr.numel() != NQ:
+        raise ValueError("index_scan_emit_fp8: one threshold per query")
+    if cand_n.numel() < NQ:
+        raise ValueError("index_scan_emit_fp8: cand_n shorter than the batch")
+    if cand_s.numel() < NQ * cap or cand_i.numel() < NQ * cap:
+        raise ValueError("index_scan_emit_fp8: candidate workspace too small")
+    if gate is not None:
+        _chk(gate, torch.int32, "gate", 1)
+    hip().index_scan_emit_fp8(_ptr(rows_u8), n_valid, D, _ptr(tiles), _ptr(n_live),
+                              _ptr(mask_words), n_rblk, _ptr(q_e4m3), NQ, _ptr(thr),
+                              _ptr(cand_s), _ptr(cand_i), _ptr(cand_n), cap,
+                              stream_handle(rows_u8.device), xcd, _ptr(gate), bool(zero_cnt))
+
+
 def tombstone_rows(rows_list: torch.Tensor, n_valid: int, dead_words: torch.Tensor,
                    slab: torch.Tensor, slab2: torch.Tensor | None = None) -> None:
     """Tombstone the listed rows (index_delete.hip): zeros over each row of ``slab`` (and of
