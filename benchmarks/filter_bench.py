@@ -34,9 +34,25 @@ Masks: all ones; uniform random bits; "documents" = runs of 200 consecutive rows
 (packed bits + live-tile list) and the gather's row list are built once per mask, outside the
 timed loops; ``mask_ms`` is that one-off cost of the RowMask.
 
+--groups 2,4,8 (bf16, k <= 32; replaces the per-mask run): a mask per query.  For every case of
+--group-cases and every G, G masks are built and the nq queries dealt over them in turn
+(query i under mask i % G); per case and G, alternated in one process:
+
+  grouped       shard.search(q, k, allow=MaskGroups): the grouped scan (index_filter_group.hip),
+                or per chunk whatever ``grouped_routes`` names (--force-scan: always the scan)
+  group_loop    the same call with the grouped scan off: one single-mask search per group, the
+                only way to answer such a burst before the grouped scan
+  union_floor   all nq queries under the union of the masks in the single-mask scan: the rows
+                the grouped scan has to walk, without its per-lane mask select
+  single_mask   all nq queries under mask 0 alone (a search that never enters the new kernel)
+
+Cases: n1 = must_not-style, each mask excludes a different 1 % of the rows (as documents);
+d1 / d0.1 = disjoint document masks of 1 % / 0.1 % each; u50 = uniform 50 %, a seed per mask.
+Every line carries grouped_equals_loop (scores bit for bit, rows outside runs of equal scores).
+
     python benchmarks/filter_bench.py [--rows 100000000] [--dim 384] [--nq 256] [--k 10]
         [--masks ones,u50,u10,u1,d10,d1,d0.1] [--rounds 3] [--iters 5] [--out FILE]
-        [--dtype bf16|fp8] [--fallback]
+        [--dtype bf16|fp8] [--fallback] [--groups 2,4,8 [--group-cases n1,d1,d0.1,u50] [--force-scan]]
 """
 from __future__ import annotations
 
@@ -110,6 +126,80 @@ def timed(fn, iters: int) -> float:
     return (time.perf_counter() - t0) / iters * 1e3
 
 
+def run_groups(a, shard, q, emit, base) -> None:
+    """The --groups run (module docstring)."""
+    dev, n, k = shard.device, a.rows, a.k
+    cls = type(shard)
+    for ci, case in enumerate(a.group_cases.split(",")):
+        for G in [int(x) for x in a.groups.split(",")]:
+            masks, taken = [], None
+            for g in range(G):
+                seed = 1000 + 37 * ci + g
+                if case[0] == "n":
+                    allow = ~build_allow("d" + case[1:], n, dev, seed)
+                else:
+                    allow = build_allow(case, n, dev, seed)
+                    if case[0] == "d":       # disjoint documents
+                        if taken is None:
+                            taken = allow.clone()
+                        else:
+                            allow &= ~taken
+                            taken |= allow
+                masks.append(shard.make_mask(allow))
+                del allow
+            del taken
+            union = masks[0].words.clone()
+            for m in masks[1:]:
+                union |= m.words
+            umask = shard.make_mask(union.view(torch.uint8))
+            group_of = [i % G for i in range(a.nq)]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            mg = shard.make_mask_groups(masks, group_of)
+            for c in range(mg.n_chunks):
+                mg.chunk(c)
+            torch.cuda.synchronize()
+            groups_ms = (time.perf_counter() - t0) * 1e3
+
+            def grouped(min_groups):
+                shard.GROUP_SCAN_MIN_GROUPS = min_groups
+                try:
+                    return shard.search(q, k, allow=mg)
+                finally:
+                    shard.GROUP_SCAN_MIN_GROUPS = cls.GROUP_SCAN_MIN_GROUPS
+
+            variants = {"grouped": lambda: grouped(2),
+                        "group_loop": lambda: grouped(1 << 30),
+                        "union_floor": lambda: shard.search(q, k, allow=umask),
+                        "single_mask": lambda: shard.search(q, k, allow=masks[0])}
+            res = {}
+            for v, fn in variants.items():       # results first (also the warm-up)
+                res[v] = fn()
+                torch.cuda.synchronize()
+            (gs, gr), (ls, lr) = res["grouped"], res["group_loop"]
+            tie = torch.zeros_like(gs, dtype=torch.bool)
+            tie[:, 1:] |= gs[:, 1:] == gs[:, :-1]
+            tie[:, :-1] |= gs[:, :-1] == gs[:, 1:]
+            same = bool(torch.equal(gs, ls) and ((gr == lr) | tie).all())
+            del res
+            routes = ["loop" if shard._loop_keeps_chunk(mg.chunk(c), k) else "scan"
+                      for c in range(mg.n_chunks)]
+            info = dict(base, case=case, groups=G, len_groups=len(mg), chunks=mg.n_chunks,
+                        grouped_routes=routes,
+                        union_live_tiles=int(umask.n_live),
+                        live_tiles=[int(m.n_live) for m in masks],
+                        groups_ms=round(groups_ms, 3), grouped_equals_loop=same)
+            times = {v: [] for v in variants}
+            for _ in range(a.rounds):            # alternated: every variant once per round
+                for v, fn in variants.items():
+                    times[v].append(timed(fn, a.iters))
+            for v, ts in times.items():
+                emit(dict(info, variant=v, ms=round(statistics.median(ts), 3),
+                          ms_min=round(min(ts), 3), ms_max=round(max(ts), 3)))
+            del masks, umask, mg, union
+            torch.cuda.empty_cache()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100_000_000)
@@ -123,6 +213,11 @@ def main() -> None:
     ap.add_argument("--dtype", choices=("bf16", "fp8"), default="bf16")
     ap.add_argument("--fallback", action="store_true",
                     help="also time the chunked matmul under the mask (one iteration)")
+    ap.add_argument("--groups", default="",
+                    help="a mask per query: comma list of group counts (replaces the per-mask run)")
+    ap.add_argument("--group-cases", default="n1,d1,d0.1,u50")
+    ap.add_argument("--force-scan", action="store_true",
+                    help="--groups: the grouped scan for every chunk, whatever the route rule")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("filter_bench needs the GPU: nothing here is measured without one")
@@ -156,6 +251,13 @@ def main() -> None:
             "rounds": a.rounds, "iters": a.iters}
     if fp8:
         base["dtype"] = "fp8"
+    if a.groups:
+        if fp8 or k > 32:
+            raise SystemExit("--groups measures the grouped bf16 list scan: bf16, k <= 32")
+        if a.force_scan:
+            shard.GROUP_LOOP_MIN_TILES = 1 << 62
+        run_groups(a, shard, q, emit, dict(base, bench="filter_bench_groups"))
+        return
     for mi, name in enumerate(a.masks.split(",")):
         allow = build_allow(name, n, dev, 100 + mi)
         torch.cuda.synchronize()

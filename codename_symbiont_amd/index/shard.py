@@ -302,6 +302,74 @@ class RowMask:
         return int(_unpack_bits(self.bits).sum())
 
 
+MASK_GROUPS = 8   # masks one grouped scan carries (index_filter_group.hip)
+
+
+class MaskGroups:
+    """A mask per query: the distinct ``RowMask``s of one search and, for each of its NQ
+    queries, which of them it runs under.  Built by ``HbmIndexShard.make_mask_groups`` and passed
+    as ``search(q, k, allow=...)``; reusable for every search with the same query-to-mask
+    assignment.
+
+    ``masks``: the distinct RowMasks (same shard, ``visible`` and ``dead_gen``).  ``group_of``:
+    host list, query i runs under ``masks[group_of[i]]``.  The grouped scan takes the masks in
+    chunks of up to MASK_GROUPS; ``chunk(c)`` builds, once, what the scan of chunk c reads:
+
+    * ``idx``: the chunk's query indices (device int64, ascending), ``qgroup``: their group
+      within the chunk (device int32);
+    * ``mask8``: int64 [n_words, 8], slot g of a tile = the word of the chunk's g-th mask;
+    * ``tiles`` / ``n_live``: ``filter_tiles`` of the OR of the chunk's masks;
+    * ``groups``: (first group, number of groups), ``nq_of``: queries per group, ``live``: the
+      live-tile counts of each mask and, last, of the union as host ints (read once when the
+      chunk is built), or None where a mask carries no tile list."""
+
+    __slots__ = ("masks", "group_of", "visible", "dead_gen", "device", "_chunks")
+
+    def __init__(self, masks: list, group_of: list):
+        self.masks, self.group_of = list(masks), [int(g) for g in group_of]
+        self.visible, self.dead_gen = masks[0].visible, masks[0].dead_gen
+        self.device = masks[0].bits.device
+        self._chunks: dict = {}
+
+    def __len__(self) -> int:
+        return len(self.masks)
+
+    @property
+    def n_chunks(self) -> int:
+        return (len(self.masks) + MASK_GROUPS - 1) // MASK_GROUPS
+
+    def queries_of(self, g: int) -> list:
+        return [i for i, x in enumerate(self.group_of) if x == g]
+
+    def chunk(self, c: int) -> dict:
+        ch = self._chunks.get(c)
+        if ch is None:
+            from ..ops.kernels import filter_tiles
+
+            g0 = c * MASK_GROUPS
+            ms = self.masks[g0:g0 + MASK_GROUPS]
+            sel = [(i, g - g0) for i, g in enumerate(self.group_of) if g0 <= g < g0 + len(ms)]
+            dev = self.device
+            words = torch.stack([m.words for m in ms], 1)             # [n_words, G_c]
+            mask8 = torch.zeros(words.shape[0], MASK_GROUPS, dtype=torch.int64, device=dev)
+            mask8[:, :len(ms)] = words
+            union = ms[0].words.clone()
+            for m in ms[1:]:
+                union.bitwise_or_(m.words)
+            tiles, n_live = filter_tiles(union, self.visible)
+            # live tiles of each mask and of the union, read once here (the route condition of
+            # HbmIndexShard._loop_keeps_chunk; no search reads the device for it)
+            live = None
+            if all(m.n_live is not None for m in ms):
+                live = torch.cat([m.n_live for m in ms] + [n_live]).tolist()
+            ch = self._chunks[c] = {
+                "idx": torch.tensor([i for i, _ in sel], dtype=torch.int64, device=dev),
+                "qgroup": torch.tensor([g for _, g in sel], dtype=torch.int32, device=dev),
+                "mask8": mask8, "tiles": tiles, "n_live": n_live, "groups": (g0, len(ms)),
+                "live": live, "nq_of": [sum(1 for _, g in sel if g == j) for j in range(len(ms))]}
+        return ch
+
+
 COMPACT_STAGE_BYTES = 256 << 20   # default staging budget of HbmIndexShard.compact
 
 
@@ -1333,7 +1401,12 @@ class HbmIndexShard:
         shard scores e4m3(q) . e4m3(x); its matmul (smaller shards at k > 32, k > 128) scores
         float(q) . decode(x).
 
+        ``allow`` may also be a ``MaskGroups`` (``make_mask_groups``): a mask per query, each
+        query exact over its own mask's rows (_search_grouped).
+
         Returns (scores f32 [NQ, k], rows int32 [NQ, k]); missing slots are (-inf, -1)."""
+        if isinstance(allow, MaskGroups):
+            return self._search_grouped(q_unit, k, n_cus, allow)
         if allow is not None:
             return self._search_masked(q_unit, k, n_cus, allow)
         if self.n_dead == 0:
@@ -1566,6 +1639,187 @@ class HbmIndexShard:
             return self._search_filtered_large_k(q_unit.to(torch.bfloat16).contiguous(), k, mask,
                                                  n_cus)
         return self._search_matmul(q_unit, k, mask=mask)
+
+    # ------------------------------------------------------------------ a row mask per query
+    # distinct masks from which a search takes the grouped scan instead of one masked search
+    # per mask (README, round 14, has the measurement behind it)
+    GROUP_SCAN_MIN_GROUPS = 2
+
+    def make_mask_groups(self, masks, group_of) -> MaskGroups:
+        """Masks and each query's mask -> ``MaskGroups``.  ``masks``: a sequence whose entries
+        are anything ``make_mask`` takes; ``group_of``: for each query of the searches to come,
+        the index into ``masks`` of the mask it runs under.  Entries that are the same object,
+        or RowMasks with equal bits, merge into one group (groups no query names are dropped).
+        All masks must be of this shard at one ``visible`` and delete generation."""
+        masks = list(masks)
+        group_of = [int(g) for g in (group_of.tolist() if hasattr(group_of, "tolist")
+                                     else group_of)]
+        if not masks:
+            raise ValueError("make_mask_groups: no masks")
+        if any(g < 0 or g >= len(masks) for g in group_of):
+            raise IndexError(f"make_mask_groups: group outside the {len(masks)} masks")
+        by_obj: dict = {}
+        made = []
+        for m in masks:
+            if id(m) not in by_obj:
+                by_obj[id(m)] = self.make_mask(m)
+            made.append(by_obj[id(m)])
+        for m in made:
+            if m.bits.device != self.device:
+                raise ValueError(f"RowMask on {m.bits.device}, shard on {self.device}")
+            if m.dead_gen != self.dead_gen:
+                raise ValueError("RowMask made before a delete (it may allow a deleted row): "
+                                 "make it again with make_mask")
+            if m.visible != made[0].visible or m.bits.numel() != made[0].bits.numel():
+                raise ValueError("make_mask_groups: masks made at different visible rows")
+        # merge: the same RowMask object first, then equal bits (one unique over the distinct
+        # objects' words, reordered to first appearance)
+        distinct, slot_of = [], {}
+        for g in group_of:
+            m = made[g]
+            if id(m) not in slot_of:
+                slot_of[id(m)] = len(distinct)
+                distinct.append(m)
+        if len(distinct) > 1:
+            inv = torch.unique(torch.stack([m.words for m in distinct]), dim=0,
+                               return_inverse=True)[1].tolist()
+            first: dict = {}
+            merged, remap = [], []
+            for j, u in enumerate(inv):
+                if u not in first:
+                    first[u] = len(merged)
+                    merged.append(distinct[j])
+                remap.append(first[u])
+        else:
+            merged, remap = distinct, [0] * len(distinct)
+        if not merged:      # no queries: keep the first mask so the object stays usable
+            merged = [made[0]]
+        return MaskGroups(merged, [remap[slot_of[id(made[g])]] for g in group_of])
+
+    def _group_scan_serves(self, k: int, groups: MaskGroups) -> bool:
+        """The grouped masked list scan serves this search (index_filter_group.hip)."""
+        return (self.device.type == "cuda" and self.dtype == "bf16" and self.dim in FILTER_DIMS
+                and 0 < k <= 32 and len(groups) >= self.GROUP_SCAN_MIN_GROUPS)
+
+    def _search_grouped(self, q_unit, k: int, n_cus, groups: MaskGroups):
+        """``search`` under a mask per query, each query exact over its own mask's rows.
+
+        * One distinct mask: ``_search_masked`` under it, unchanged.
+        * A bf16 GPU shard of width 384 / 768 / 1024 at k <= 32 with GROUP_SCAN_MIN_GROUPS
+          masks or more: the grouped masked list scan, one scan of the union's live tiles per
+          chunk of up to 8 masks over that chunk's queries (_search_group_chunk).  It scores
+          bf16(q) . bf16(x) with the MFMA chain of the single-mask scan, bit for bit alike.
+          (A chunk of two to four large disjoint masks whose queries grouping would spread
+          over one more query block stays with the next route: _loop_keeps_chunk.)
+        * Everything else: one ``_search_masked`` per mask over its queries, scattered back.
+          Those are the existing routes, exact as they stand: a CPU shard, k > 128, other
+          widths and small fp8 shards at k > 32 score float(q) . float(x) (fp8:
+          float(q) . decode(x)) in the masked matmul; a GPU fp8 shard's list scan (k <= 32) and
+          emitting scan (32 < k <= 128) score e4m3(q) . e4m3(x); a bf16 GPU shard at
+          32 < k <= 128 takes the masked emitting scan, bf16(q) . bf16(x).
+
+        Tombstones need nothing here: ``make_mask`` clears them in every mask, and a
+        ``MaskGroups`` from before a later delete is refused as a RowMask is."""
+        NQ = q_unit.shape[0]
+        k = int(k)
+        if len(groups.group_of) != NQ:
+            raise ValueError(f"MaskGroups for {len(groups.group_of)} queries, search has {NQ}")
+        if groups.device != self.device:
+            raise ValueError(f"RowMask on {groups.device}, shard on {self.device}")
+        if groups.dead_gen != self.dead_gen:
+            raise ValueError("RowMask made before a delete (it may allow a deleted row): make "
+                             "it again with make_mask")
+        if NQ == 0 or k <= 0:
+            return (torch.empty(NQ, max(k, 0), device=self.device),
+                    torch.empty(NQ, max(k, 0), dtype=torch.int32, device=self.device))
+        if len(groups) == 1:
+            return self._search_masked(q_unit, k, n_cus, groups.masks[0])
+        out_s = torch.empty(NQ, k, device=self.device)
+        out_i = torch.empty(NQ, k, dtype=torch.int32, device=self.device)
+        def loop(g0, g1):
+            for g in range(g0, g1):
+                idx = torch.tensor(groups.queries_of(g), dtype=torch.int64, device=self.device)
+                s, i = self._search_masked(q_unit[idx], k, n_cus, groups.masks[g])
+                out_s[idx], out_i[idx] = s, i.to(torch.int32)
+
+        if self._group_scan_serves(k, groups):
+            q = q_unit.to(torch.bfloat16).contiguous()
+            for c in range(groups.n_chunks):
+                ch = groups.chunk(c)
+                if self._loop_keeps_chunk(ch, k):
+                    loop(ch["groups"][0], sum(ch["groups"]))
+                    continue
+                s, i = self._search_group_chunk(q[ch["idx"]], k, groups, ch, n_cus)
+                out_s[ch["idx"]], out_i[ch["idx"]] = s, i
+            return out_s, out_i
+        loop(0, len(groups))
+        return out_s, out_i
+
+    # The measured case the per-mask loop keeps (README, round 14): a chunk of two to four masks
+    # whose tiles are disjoint, on a width where each group's queries fit one query block but
+    # all of them together need two (768 / 1024 above 128 queries).  The loop then walks each
+    # mask's tiles once with one block; the grouped scan walks the union with both blocks, half
+    # of it for nothing.  At 50M x 768 under disjoint 1 % document masks the two tied at 2 and 4
+    # groups (0.713 / 1.317 against 0.709 / 1.347 ms in one run, 0.688 / 1.325 against
+    # 0.689 / 1.310 in the next; 20 263 / 39 986 union tiles), the scan led by 5-6 % at 8 groups
+    # in both, and by 2.1x at 2 052 union tiles, where the launches dominate: the tile floor
+    # sits between 2 052 and 20 263.
+    GROUP_LOOP_MAX_GROUPS = 4
+    GROUP_LOOP_MIN_TILES = 16384
+
+    def _loop_keeps_chunk(self, ch: dict, k: int) -> bool:
+        from ..ops._ext import hip
+
+        live = ch["live"]
+        if live is None or not 2 <= len(ch["nq_of"]) <= self.GROUP_LOOP_MAX_GROUPS:
+            return False
+        _, qpb = hip().topk_geometry(self.dim, 16 if k <= 16 else 32)
+        blocks = lambda nq: (nq + qpb - 1) // qpb
+        union = live[-1]
+        return (blocks(sum(ch["nq_of"])) > max(blocks(nq) for nq in ch["nq_of"])
+                and union >= self.GROUP_LOOP_MIN_TILES and union >= 0.9 * sum(live[:-1]))
+
+    def _search_group_chunk(self, q_unit, k: int, groups: MaskGroups, ch: dict, n_cus):
+        """The grouped masked list scan over one chunk's queries + merge: _search_filtered with
+        the chunk's eight mask words per tile and the union's live-tile list (same grid sizing,
+        same seed pass, whose k-th best per query is a lower bound under that query's own
+        mask)."""
+        from ..ops import kernels as K
+        from ..ops._ext import hip, stream_handle
+
+        h, dev = hip(), self.device
+        NQ = q_unit.shape[0]
+        kmax = 16 if k <= 16 else 32
+        n = min(groups.visible, self.visible)
+        out_s = torch.empty(NQ, k, device=dev)
+        out_i = torch.empty(NQ, k, dtype=torch.int32, device=dev)
+        if n <= 0:
+            return out_s.fill_(-math.inf), out_i.fill_(-1)
+        lists, qpb = h.topk_geometry(self.dim, kmax)
+        n_qblk = math.ceil(NQ / qpb)
+        if n_cus is None:
+            n_cus = self._n_cus()
+        n_rblk = max(1, min(math.ceil(n / (TILE_ROWS * self.FILTER_MIN_TILES)),
+                            max(1, round(n_cus / n_qblk))))
+        ncand = n_rblk * lists * kmax
+        cs = torch.empty(NQ, ncand, device=dev)
+        ci = torch.empty(NQ, ncand, dtype=torch.int32, device=dev)
+        st = stream_handle(dev)
+
+        def one_pass(thr, stride):
+            K.index_scan_filter_group(self.rows, n, ch["mask8"], ch["qgroup"], ch["tiles"],
+                                      ch["n_live"], q_unit, kmax, n_rblk, cs, ci, thr, stride,
+                                      self.scan_xcd)
+            h.topk_merge(cs.data_ptr(), ci.data_ptr(), NQ, ncand, kmax, k, out_s.data_ptr(),
+                         out_i.data_ptr(), 0, 0, st, 0)
+
+        thr = None
+        if self.filter_seed:
+            one_pass(None, self.FILTER_SEED_STRIDE)
+            kth = out_s[:, k - 1].contiguous()
+            thr = torch.nextafter(kth, torch.full_like(kth, -math.inf))
+        one_pass(thr, 1)
+        return out_s, out_i
 
     # seed pass of the masked large-k search: every S-th live tile of each workgroup's slice.
     # 32 is the unmasked route's sample rate (PRUNE_TILE_SHIFT = 5).  A query emits about k * S

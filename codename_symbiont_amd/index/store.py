@@ -90,6 +90,7 @@ class VectorStore:
         # RowMasks of recent filters, by filter value (LRU); dropped whole by every upsert: an
         # overwritten row may have changed documents, an appended one may match
         self._masks: collections.OrderedDict = collections.OrderedDict()
+        self._mask_groups = None     # the last per-query search's (signature, MaskGroups, masks)
         # SYMB_SEARCH_PIPELINE (default on, single GPU shard): a search's query-side pre-pass
         # (HbmIndexShard.search_begin) runs on one stream and its full-shard scan (search_end) on
         # another, so with the service's two scans in flight the next burst's pre-pass runs
@@ -162,6 +163,7 @@ class VectorStore:
         for r in rows:
             self._frag.pop(r, None)
         self._masks.clear()      # every cached mask may allow a row that is now dead
+        self._mask_groups = None
         return n
 
     def delete(self, point_ids: list[str] | None = None, filter: Filter | None = None) -> int:
@@ -242,6 +244,7 @@ class VectorStore:
                 torch.cuda.synchronize(self.shard.device)
             self._frag.clear()       # cached by row
             self._masks.clear()
+            self._mask_groups = None
             job = self._cut_locked() if self.dir and snapshot else None
         self._start(job, background=False)
         return n
@@ -266,6 +269,7 @@ class VectorStore:
         for g in out or ():
             self._frag.pop(int(g), None)   # (re)written rows: their cached result JSON is stale
         self._masks.clear()
+        self._mask_groups = None
         return out
 
     def upsert(self, point_ids: list[str], vecs: np.ndarray, payloads: list[Payload]) -> None:
@@ -373,7 +377,13 @@ class VectorStore:
         exact over them, and slots past the passing points are (-inf, -1).  On a bf16 GPU shard of
         width 384 / 768 / 1024 a filtered search, and any search after a ``delete``, stays on the
         HIP scans up to k = 128 (HbmIndexShard._search_masked / _search_tombstoned); so does every
-        search of an fp8 GPU shard of 2^20 rows or more (k <= 32 at any size)."""
+        search of an fp8 GPU shard of 2^20 rows or more (k <= 32 at any size).
+
+        ``filter`` may also be a list or tuple of nq entries, each a Filter or None: query i is
+        searched under entry i.  Queries whose entry is None take the plain unfiltered search
+        together (entry None returns what ``search(q_i, k)`` returns); the others run as ONE
+        search under a mask per query (HbmIndexShard._search_grouped), on a bf16 GPU shard of
+        width 384 / 768 / 1024 at k <= 32 one grouped scan per 8 distinct filters."""
         if filter is not None and self.group is not None:
             raise ValueError("filtered search is single-shard for now: this store searches a "
                              "multi-GPU group")
@@ -384,9 +394,54 @@ class VectorStore:
             raise DimensionError(f"Wrong input: Vector dimension error: expected dim: {self.dim}, "
                                  f"got {q.shape[1]}")
         k = int(k)
+        per_query = isinstance(filter, (list, tuple))
+        if per_query:
+            if len(filter) != q.shape[0]:
+                raise ValueError(f"{len(filter)} filters for {q.shape[0]} queries")
+            for f in filter:
+                if f is not None and not isinstance(f, Filter):
+                    raise TypeError("filter entries must be index.filter.Filter or None, got "
+                                    f"{type(f).__name__}")
         if k <= 0 or self.count == 0:
             return np.zeros((q.shape[0], 0), np.float32), np.zeros((q.shape[0], 0), np.int64)
+        if per_query:
+            return self._search_per_query(q, k, list(filter))
         kw = {"allow": self._mask_for(filter)} if filter is not None else {}
+        return self._search_allow(q, k, kw)
+
+    def _search_per_query(self, q: np.ndarray, k: int, filters: list):
+        """search() under a Filter (or None) per query: the None entries by one unfiltered
+        search, the rest by one search under a ``MaskGroups`` of the distinct filters' masks
+        (filters are equal when their ``key()`` is)."""
+        nq = q.shape[0]
+        plain = [i for i, f in enumerate(filters) if f is None]
+        if len(plain) == nq:
+            return self._search_allow(q, k, {})
+        out_s = np.full((nq, k), -np.inf, np.float32)
+        out_r = np.full((nq, k), -1, np.int64)
+        if plain:
+            out_s[plain], out_r[plain] = self._search_allow(q[plain], k, {})
+        rest = [i for i, f in enumerate(filters) if f is not None]
+        slot: dict = {}
+        masks, group_of = [], []     # (held here while building: the LRU keeps 16)
+        for i in rest:
+            key = filters[i].key()
+            if key not in slot:
+                slot[key] = len(masks)
+                masks.append(self._mask_for(filters[i]))
+            group_of.append(slot[key])
+        sig = (tuple(id(m) for m in masks), tuple(group_of))
+        cached = self._mask_groups
+        if cached is not None and cached[0] == sig:
+            groups = cached[1]
+        else:     # (the MaskGroups holds its masks, so the ids of `sig` stay theirs)
+            groups = self.shard.make_mask_groups(masks, group_of)
+            self._mask_groups = (sig, groups, masks)
+        out_s[rest], out_r[rest] = self._search_allow(q[rest], k, {"allow": groups})
+        return out_s, out_r
+
+    def _search_allow(self, q: np.ndarray, k: int, kw: dict):
+        """search() of validated queries under the shard's ``allow`` argument (or none)."""
         if self._streams is not None:
             return self._search_pipelined(q, k, **kw)
         qt = torch.nn.functional.normalize(torch.from_numpy(q).to(self.shard.device), dim=-1)

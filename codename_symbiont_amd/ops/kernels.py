@@ -320,6 +320,60 @@ def index_scan_filter(rows: torch.Tensor, n_valid: int, mask_words: torch.Tensor
                             stream_handle(rows.device), _ptr(thr_init), xcd, _ptr(gate))
 
 
+MASK_GROUPS = 8   # mask words per tile of the grouped masked scan (index_filter_group.hip)
+
+
+def index_scan_filter_group(rows: torch.Tensor, n_valid: int, mask8: torch.Tensor,
+                            qgroup: torch.Tensor, tiles: torch.Tensor, n_live: torch.Tensor,
+                            q_unit: torch.Tensor, kmax: int, n_rblk: int, cand_s: torch.Tensor,
+                            cand_i: torch.Tensor, thr_init: torch.Tensor | None = None,
+                            stride: int = 1, xcd: int = 1,
+                            gate: torch.Tensor | None = None) -> None:
+    """``index_scan_filter`` under a mask per query: ``mask8`` int64 [n_words, 8] holds, for
+    each 64-row tile, the mask word of each of up to 8 groups (unused slots 0), and ``qgroup``
+    int32 [NQ] names each query's group (its low three bits are used).  ``tiles`` / ``n_live``
+    are ``filter_tiles`` of the OR of the eight slots.  Query q's candidates are those of
+    ``index_scan_filter`` under slot ``qgroup[q]``'s words, scored bit for bit alike."""
+    _chk(rows, torch.bfloat16, "rows", 2)
+    _chk(q_unit, torch.bfloat16, "q_unit", 2)
+    _chk(mask8, torch.int64, "mask8", 2)
+    _chk(qgroup, torch.int32, "qgroup", 1)
+    _chk(tiles, torch.int32, "tiles", 1)
+    _chk(n_live, torch.int32, "n_live", 1)
+    _chk(cand_s, torch.float32, "cand_s")
+    _chk(cand_i, torch.int32, "cand_i")
+    D = rows.shape[1]
+    NQ = q_unit.shape[0]
+    n_valid, n_rblk, stride = int(n_valid), int(n_rblk), int(stride)
+    if D not in FILTER_DIMS or q_unit.shape[1] != D:
+        raise ValueError(f"index_scan_filter_group: rows must be {FILTER_DIMS} wide, queries alike")
+    if kmax not in (16, 32) or stride < 1 or n_rblk < 1:
+        raise ValueError("index_scan_filter_group: kmax in (16, 32), stride >= 1, n_rblk >= 1")
+    if mask8.shape[1] != MASK_GROUPS or not mask8.is_contiguous():
+        raise ValueError("index_scan_filter_group: mask8 must be contiguous "
+                         f"[n_words, {MASK_GROUPS}]")
+    if qgroup.numel() != NQ:
+        raise ValueError("index_scan_filter_group: qgroup must hold one group per query")
+    n_tiles = (n_valid + 63) // 64
+    # every tile the list can name lies inside the row slab and has its eight mask words
+    if n_tiles * 64 > rows.shape[0] or n_tiles > mask8.shape[0] or n_tiles > tiles.numel():
+        raise ValueError("index_scan_filter_group: rows / mask8 / tile list shorter than n_valid")
+    lists, _ = hip().topk_geometry(D, kmax)
+    need = NQ * n_rblk * lists * kmax
+    if cand_s.numel() < need or cand_i.numel() < need:
+        raise ValueError("index_scan_filter_group: candidate workspace too small")
+    if thr_init is not None:
+        _chk(thr_init, torch.float32, "thr_init", 1)
+        if thr_init.numel() < NQ:
+            raise ValueError("index_scan_filter_group: thr_init shorter than the batch")
+    if gate is not None:
+        _chk(gate, torch.int32, "gate", 1)
+    hip().index_scan_filter_group(_ptr(rows), n_valid, D, _ptr(tiles), _ptr(n_live), _ptr(mask8),
+                                  _ptr(qgroup), stride, n_rblk, _ptr(q_unit), NQ, kmax,
+                                  _ptr(cand_s), _ptr(cand_i), stream_handle(rows.device),
+                                  _ptr(thr_init), xcd, _ptr(gate))
+
+
 FILTER_LARGE_K_DIMS = (384, 768, 1024)   # ... of the masked emitting scan (index_mq_filter.hip)
 # (sets, rsplit) forms it is built for, per width
 _MQ_FILTER_FORMS = {384: ((4, 1), (4, 2)), 768: ((2, 1),), 1024: ((1, 1),)}

@@ -142,6 +142,38 @@ def filtered_topk_ref(index_rows: torch.Tensor, queries: torch.Tensor, k: int,
     return v, torch.where(torch.isfinite(v), i, torch.full_like(i, -1))
 
 
+def grouped_filtered_topk_ref(index_rows: torch.Tensor, queries: torch.Tensor, k: int, allows,
+                              group_of):
+    """``filtered_topk_ref`` under a mask per query: ``allows`` is a sequence of bool [n] masks
+    (or a bool [G, n] tensor) and ``group_of`` [NQ] names each query's mask.  Query i's result
+    is the exact top-k over the rows ``allows[group_of[i]]`` marks.  Always [NQ, k]; slots past
+    a query's allowed rows are (-inf, -1)."""
+    dev = index_rows.device
+    qf = queries.float()
+    n, NQ = index_rows.shape[0], qf.shape[0]
+    allow = torch.stack([torch.as_tensor(a, dtype=torch.bool, device=dev) for a in allows]) \
+        if not isinstance(allows, torch.Tensor) else allows.to(dev, torch.bool)
+    if allow.dim() != 2 or allow.shape[1] != n:
+        raise ValueError(f"grouped_filtered_topk_ref: masks {tuple(allow.shape)} for {n} rows")
+    g = torch.as_tensor(group_of, dtype=torch.int64, device=dev).flatten()
+    if g.numel() != NQ:
+        raise ValueError(f"grouped_filtered_topk_ref: {g.numel()} groups for {NQ} queries")
+    if NQ and (int(g.min()) < 0 or int(g.max()) >= allow.shape[0]):
+        raise IndexError("grouped_filtered_topk_ref: group outside the masks")
+    chunk = max(4096, (1 << 26) // max(1, NQ))
+    vs = [torch.full((NQ, k), -math.inf, device=dev)]
+    ix = [torch.full((NQ, k), -1, dtype=torch.int64, device=dev)]
+    for s in range(0, n, chunk):
+        sc = qf @ index_rows[s:s + chunk].float().t()
+        sc.masked_fill_(~allow[:, s:s + chunk][g], -math.inf)
+        v, i = torch.topk(sc, min(k, sc.shape[1]), dim=1)
+        vs.append(v)
+        ix.append(i + s)
+    v, j = torch.topk(torch.cat(vs, 1), k, dim=1)
+    i = torch.gather(torch.cat(ix, 1), 1, j)
+    return v, torch.where(torch.isfinite(v), i, torch.full_like(i, -1))
+
+
 def row_scores_ref(index_rows: torch.Tensor, queries: torch.Tensor, r: torch.Tensor):
     """Exact fp32 scores of the rows r [NQ, k] a search returned (no full score matrix)."""
     if r.numel() and int(r.min()) < 0:

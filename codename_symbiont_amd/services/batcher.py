@@ -237,13 +237,19 @@ class _SReq:
     q: np.ndarray
     k: int
     fut: asyncio.Future
+    filter: object = None
 
 
 class SearchBatcher:
-    """Coalesce concurrent searches into one fused scan (Q up to ``max_q`` queries per launch)."""
+    """Coalesce concurrent searches into one fused scan (Q up to ``max_q`` queries per launch).
+
+    A request may carry a filter (``index.filter.Filter``).  A batch none of whose requests has
+    one calls ``search_fn(qs, k)``; any other calls ``search_fn(qs, k, filters)`` with one entry
+    (Filter or None) per query -- ``VectorStore.search``'s per-query form."""
 
     def __init__(self, search_fn, window_ms: float = 1.0, max_q: int = 256, metrics=None):
-        self.search_fn = search_fn  # (np.ndarray [nq, D] f32, k) -> (scores [nq,k], ids [nq,k])
+        # (np.ndarray [nq, D] f32, k[, filters]) -> (scores [nq,k], ids [nq,k])
+        self.search_fn = search_fn
         self.window = window_ms / 1000.0
         self.max_q = max_q
         self.metrics = metrics
@@ -251,16 +257,19 @@ class SearchBatcher:
         self._task = None
         self._last_end = float("-inf")
 
-    async def search(self, q: np.ndarray, k: int):
+    async def search(self, q: np.ndarray, k: int, filter=None):
         if self._task is None:
             self._task = asyncio.create_task(self._run())
         fut = asyncio.get_running_loop().create_future()
-        await self._q.put(_SReq(np.asarray(q, np.float32).reshape(1, -1), int(k), fut))
+        await self._q.put(_SReq(np.asarray(q, np.float32).reshape(1, -1), int(k), fut,
+                               filter))
         return await fut
 
-    def _timed_search(self, qs, k):
+    def _timed_search(self, qs, k, filters=None):
         with stage("index_search", self.metrics, nq=len(qs), k=k):
-            return self.search_fn(qs, k)
+            if filters is None:
+                return self.search_fn(qs, k)
+            return self.search_fn(qs, k, filters)
 
     async def _run(self) -> None:
         loop = asyncio.get_running_loop()
@@ -270,8 +279,11 @@ class SearchBatcher:
                                    lambda b: len(b) >= self.max_q)
             kmax = max(r.k for r in batch)
             qs = np.concatenate([r.q for r in batch], 0)
+            filters = [r.filter for r in batch]
+            if all(f is None for f in filters):
+                filters = None
             try:
-                s, i = await loop.run_in_executor(None, self._timed_search, qs, kmax)
+                s, i = await loop.run_in_executor(None, self._timed_search, qs, kmax, filters)
             except Exception as e:
                 self._last_end = loop.time()
                 for j, r in enumerate(batch):
