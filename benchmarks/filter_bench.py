@@ -34,12 +34,13 @@ Masks: all ones; uniform random bits; "documents" = runs of 200 consecutive rows
 (packed bits + live-tile list) and the gather's row list are built once per mask, outside the
 timed loops; ``mask_ms`` is that one-off cost of the RowMask.
 
---groups 2,4,8 (bf16, k <= 32; replaces the per-mask run): a mask per query.  For every case of
+--groups 2,4,8 (bf16 or --dtype fp8, k <= 32; replaces the per-mask run): a mask per query.  For every case of
 --group-cases and every G, G masks are built and the nq queries dealt over them in turn
 (query i under mask i % G); per case and G, alternated in one process:
 
-  grouped       shard.search(q, k, allow=MaskGroups): the grouped scan (index_filter_group.hip),
-                or per chunk whatever ``grouped_routes`` names (--force-scan: always the scan)
+  grouped       shard.search(q, k, allow=MaskGroups): the grouped scan (index_filter_group.hip;
+                index_filter_group_fp8.hip on an fp8 shard), or per chunk whatever
+                ``grouped_routes`` names (--force-scan: always the scan)
   group_loop    the same call with the grouped scan off: one single-mask search per group, the
                 only way to answer such a burst before the grouped scan
   union_floor   all nq queries under the union of the masks in the single-mask scan: the rows
@@ -48,7 +49,9 @@ timed loops; ``mask_ms`` is that one-off cost of the RowMask.
 
 Cases: n1 = must_not-style, each mask excludes a different 1 % of the rows (as documents);
 d1 / d0.1 = disjoint document masks of 1 % / 0.1 % each; u50 = uniform 50 %, a seed per mask.
-Every line carries grouped_equals_loop (scores bit for bit, rows outside runs of equal scores).
+Every line carries grouped_equals_loop (scores bit for bit, rows outside runs of equal scores;
+on fp8 a last slot that differs without an equal neighbour must be proved a tie as above, and
+last_slot_ties_proved counts them).
 
     python benchmarks/filter_bench.py [--rows 100000000] [--dim 384] [--nq 256] [--k 10]
         [--masks ones,u50,u10,u1,d10,d1,d0.1] [--rounds 3] [--iters 5] [--out FILE]
@@ -181,6 +184,9 @@ def run_groups(a, shard, q, emit, base) -> None:
             tie[:, 1:] |= gs[:, 1:] == gs[:, :-1]
             tie[:, :-1] |= gs[:, :-1] == gs[:, 1:]
             same = bool(torch.equal(gs, ls) and ((gr == lr) | tie).all())
+            proved = None
+            if shard.dtype == "fp8" and torch.equal(gs, ls) and not same:
+                same, proved = rows_equal_outside_ties(shard, q, gs, gr, lr)
             del res
             routes = ["loop" if shard._loop_keeps_chunk(mg.chunk(c), k) else "scan"
                       for c in range(mg.n_chunks)]
@@ -189,6 +195,8 @@ def run_groups(a, shard, q, emit, base) -> None:
                         union_live_tiles=int(umask.n_live),
                         live_tiles=[int(m.n_live) for m in masks],
                         groups_ms=round(groups_ms, 3), grouped_equals_loop=same)
+            if proved is not None:
+                info["last_slot_ties_proved"] = proved
             times = {v: [] for v in variants}
             for _ in range(a.rounds):            # alternated: every variant once per round
                 for v, fn in variants.items():
@@ -252,8 +260,8 @@ def main() -> None:
     if fp8:
         base["dtype"] = "fp8"
     if a.groups:
-        if fp8 or k > 32:
-            raise SystemExit("--groups measures the grouped bf16 list scan: bf16, k <= 32")
+        if k > 32:
+            raise SystemExit("--groups measures the grouped list scans: k <= 32")
         if a.force_scan:
             shard.GROUP_LOOP_MIN_TILES = 1 << 62
         run_groups(a, shard, q, emit, dict(base, bench="filter_bench_groups"))

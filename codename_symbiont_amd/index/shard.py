@@ -302,7 +302,7 @@ class RowMask:
         return int(_unpack_bits(self.bits).sum())
 
 
-MASK_GROUPS = 8   # masks one grouped scan carries (index_filter_group.hip)
+MASK_GROUPS = 8   # masks one grouped scan carries (index_filter_group.hip, ..._group_fp8.hip)
 
 
 class MaskGroups:
@@ -312,8 +312,10 @@ class MaskGroups:
     assignment.
 
     ``masks``: the distinct RowMasks (same shard, ``visible`` and ``dead_gen``).  ``group_of``:
-    host list, query i runs under ``masks[group_of[i]]``.  The grouped scan takes the masks in
-    chunks of up to MASK_GROUPS; ``chunk(c)`` builds, once, what the scan of chunk c reads:
+    host list, query i runs under ``masks[group_of[i]]``.  The grouped scan (of a bf16 or an fp8
+    GPU shard alike: the words and the tile list do not depend on the row format) takes the
+    masks in chunks of up to MASK_GROUPS; ``chunk(c)`` builds, once, what the scan of chunk c
+    reads:
 
     * ``idx``: the chunk's query indices (device int64, ascending), ``qgroup``: their group
       within the chunk (device int32);
@@ -1697,26 +1699,32 @@ class HbmIndexShard:
         return MaskGroups(merged, [remap[slot_of[id(made[g])]] for g in group_of])
 
     def _group_scan_serves(self, k: int, groups: MaskGroups) -> bool:
-        """The grouped masked list scan serves this search (index_filter_group.hip)."""
-        return (self.device.type == "cuda" and self.dtype == "bf16" and self.dim in FILTER_DIMS
-                and 0 < k <= 32 and len(groups) >= self.GROUP_SCAN_MIN_GROUPS)
+        """The grouped masked list scan serves this search (bf16: index_filter_group.hip; fp8:
+        index_filter_group_fp8.hip, built at every width and both kmax of the single-mask fp8
+        scan)."""
+        if (self.device.type != "cuda" or not 0 < k <= 32
+                or len(groups) < self.GROUP_SCAN_MIN_GROUPS):
+            return False
+        return ((self.dtype == "bf16" and self.dim in FILTER_DIMS)
+                or (self.dtype == "fp8" and self.dim in FILTER_FP8_DIMS))
 
     def _search_grouped(self, q_unit, k: int, n_cus, groups: MaskGroups):
         """``search`` under a mask per query, each query exact over its own mask's rows.
 
         * One distinct mask: ``_search_masked`` under it, unchanged.
-        * A bf16 GPU shard of width 384 / 768 / 1024 at k <= 32 with GROUP_SCAN_MIN_GROUPS
-          masks or more: the grouped masked list scan, one scan of the union's live tiles per
-          chunk of up to 8 masks over that chunk's queries (_search_group_chunk).  It scores
-          bf16(q) . bf16(x) with the MFMA chain of the single-mask scan, bit for bit alike.
+        * A GPU shard at k <= 32 with GROUP_SCAN_MIN_GROUPS masks or more -- bf16 of width
+          384 / 768 / 1024, or fp8 of width 256 / 384 / 512 / 768 / 1024: the grouped masked list
+          scan of its row format, one scan of the union's live tiles per chunk of up to 8 masks
+          over that chunk's queries (_search_group_chunk).  It scores bf16(q) . bf16(x), on fp8
+          e4m3(q) . e4m3(x), with the MFMA chain of the single-mask scan, bit for bit alike.
           (A chunk of two to four large disjoint masks whose queries grouping would spread
           over one more query block stays with the next route: _loop_keeps_chunk.)
         * Everything else: one ``_search_masked`` per mask over its queries, scattered back.
           Those are the existing routes, exact as they stand: a CPU shard, k > 128, other
           widths and small fp8 shards at k > 32 score float(q) . float(x) (fp8:
-          float(q) . decode(x)) in the masked matmul; a GPU fp8 shard's list scan (k <= 32) and
-          emitting scan (32 < k <= 128) score e4m3(q) . e4m3(x); a bf16 GPU shard at
-          32 < k <= 128 takes the masked emitting scan, bf16(q) . bf16(x).
+          float(q) . decode(x)) in the masked matmul; a GPU fp8 shard's emitting scan
+          (32 < k <= 128) scores e4m3(q) . e4m3(x); a bf16 GPU shard at 32 < k <= 128 takes the
+          masked emitting scan, bf16(q) . bf16(x).
 
         Tombstones need nothing here: ``make_mask`` clears them in every mask, and a
         ``MaskGroups`` from before a later delete is refused as a RowMask is."""
@@ -1744,6 +1752,11 @@ class HbmIndexShard:
 
         if self._group_scan_serves(k, groups):
             q = q_unit.to(torch.bfloat16).contiguous()
+            if self.dtype == "fp8":
+                # e4m3 bytes, once per search (as _search_filtered quantises them per mask)
+                from ..ops.kernels import quant_fp8
+
+                q = quant_fp8(q, scale=FP8_SCALE)
             for c in range(groups.n_chunks):
                 ch = groups.chunk(c)
                 if self._loop_keeps_chunk(ch, k):
@@ -1763,7 +1776,11 @@ class HbmIndexShard:
     # groups (0.713 / 1.317 against 0.709 / 1.347 ms in one run, 0.688 / 1.325 against
     # 0.689 / 1.310 in the next; 20 263 / 39 986 union tiles), the scan led by 5-6 % at 8 groups
     # in both, and by 2.1x at 2 052 union tiles, where the launches dominate: the tile floor
-    # sits between 2 052 and 20 263.
+    # sits between 2 052 and 20 263.  An fp8 shard has 256 queries per block at every width, so
+    # its case starts above 256 queries; there the scan does not tie but lose (README, round 15:
+    # 100M rows, 512 queries, disjoint 1 % masks, 2 / 4 groups: 1.571 / 2.819 against the loop's
+    # 1.042 / 1.898 ms at 1024, 1.019 / 1.702 against 0.741 / 1.361 at 384), so the same
+    # constants serve it; 8 groups and the tile floor are unmeasured on fp8.
     GROUP_LOOP_MAX_GROUPS = 4
     GROUP_LOOP_MIN_TILES = 16384
 
@@ -1773,7 +1790,10 @@ class HbmIndexShard:
         live = ch["live"]
         if live is None or not 2 <= len(ch["nq_of"]) <= self.GROUP_LOOP_MAX_GROUPS:
             return False
-        _, qpb = hip().topk_geometry(self.dim, 16 if k <= 16 else 32)
+        # queries per block of the scans: 256 on fp8 (the rule can then hold above 256 queries
+        # only), topk_geometry's on bf16
+        qpb = 256 if self.dtype == "fp8" else hip().topk_geometry(
+            self.dim, 16 if k <= 16 else 32)[1]
         blocks = lambda nq: (nq + qpb - 1) // qpb
         union = live[-1]
         return (blocks(sum(ch["nq_of"])) > max(blocks(nq) for nq in ch["nq_of"])
@@ -1783,7 +1803,9 @@ class HbmIndexShard:
         """The grouped masked list scan over one chunk's queries + merge: _search_filtered with
         the chunk's eight mask words per tile and the union's live-tile list (same grid sizing,
         same seed pass, whose k-th best per query is a lower bound under that query's own
-        mask)."""
+        mask).  On an fp8 shard ``q_unit`` holds the queries' e4m3 bytes (quantised once per
+        search by _search_grouped), and the raw scores, S^2 * cosine, are rescaled once at the
+        end."""
         from ..ops import kernels as K
         from ..ops._ext import hip, stream_handle
 
@@ -1795,7 +1817,11 @@ class HbmIndexShard:
         out_i = torch.empty(NQ, k, dtype=torch.int32, device=dev)
         if n <= 0:
             return out_s.fill_(-math.inf), out_i.fill_(-1)
-        lists, qpb = h.topk_geometry(self.dim, kmax)
+        fp8 = self.dtype == "fp8"
+        if fp8:
+            scan, (lists, qpb) = K.index_scan_filter_group_fp8, (2, 256)
+        else:
+            scan, (lists, qpb) = K.index_scan_filter_group, h.topk_geometry(self.dim, kmax)
         n_qblk = math.ceil(NQ / qpb)
         if n_cus is None:
             n_cus = self._n_cus()
@@ -1807,9 +1833,8 @@ class HbmIndexShard:
         st = stream_handle(dev)
 
         def one_pass(thr, stride):
-            K.index_scan_filter_group(self.rows, n, ch["mask8"], ch["qgroup"], ch["tiles"],
-                                      ch["n_live"], q_unit, kmax, n_rblk, cs, ci, thr, stride,
-                                      self.scan_xcd)
+            scan(self.rows, n, ch["mask8"], ch["qgroup"], ch["tiles"], ch["n_live"], q_unit,
+                 kmax, n_rblk, cs, ci, thr, stride, self.scan_xcd)
             h.topk_merge(cs.data_ptr(), ci.data_ptr(), NQ, ncand, kmax, k, out_s.data_ptr(),
                          out_i.data_ptr(), 0, 0, st, 0)
 
@@ -1819,6 +1844,8 @@ class HbmIndexShard:
             kth = out_s[:, k - 1].contiguous()
             thr = torch.nextafter(kth, torch.full_like(kth, -math.inf))
         one_pass(thr, 1)
+        if fp8:
+            out_s.mul_(1.0 / (FP8_SCALE * FP8_SCALE))   # (-inf stays -inf)
         return out_s, out_i
 
     # seed pass of the masked large-k search: every S-th live tile of each workgroup's slice.

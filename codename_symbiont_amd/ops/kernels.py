@@ -480,6 +480,66 @@ def index_scan_filter_fp8(rows_u8: torch.Tensor, n_valid: int, mask_words: torch
                                 _ptr(thr_init), xcd, _ptr(gate))
 
 
+def index_scan_filter_group_fp8(rows_u8: torch.Tensor, n_valid: int, mask8: torch.Tensor,
+                                qgroup: torch.Tensor, tiles: torch.Tensor, n_live: torch.Tensor,
+                                q_e4m3: torch.Tensor, kmax: int, n_rblk: int,
+                                cand_s: torch.Tensor, cand_i: torch.Tensor,
+                                thr_init: torch.Tensor | None = None, stride: int = 1,
+                                xcd: int = 1, gate: torch.Tensor | None = None) -> None:
+    """``index_scan_filter_fp8`` under a mask per query (index_filter_group_fp8.hip): ``mask8``
+    int64 [n_words, 8] and ``qgroup`` int32 [NQ] as in ``index_scan_filter_group``, ``tiles`` /
+    ``n_live`` ``filter_tiles`` of the OR of the eight slots.  Query q's candidates
+    [NQ][n_rblk][2][kmax] are those of ``index_scan_filter_fp8`` under slot ``qgroup[q]``'s
+    words, raw accumulators scored bit for bit alike; ``thr_init`` in the same units."""
+    if rows_u8.dtype != torch.uint8 or q_e4m3.dtype != torch.uint8:
+        # (a bf16 slab of the same width would be read as twice as many e4m3 rows)
+        raise ValueError("index_scan_filter_group_fp8: rows and queries are e4m3 bytes (uint8), "
+                         f"got {rows_u8.dtype} / {q_e4m3.dtype}")
+    _chk(rows_u8, torch.uint8, "rows_u8", 2)
+    _chk(q_e4m3, torch.uint8, "q_e4m3", 2)
+    _chk(mask8, torch.int64, "mask8", 2)
+    _chk(qgroup, torch.int32, "qgroup", 1)
+    _chk(tiles, torch.int32, "tiles", 1)
+    _chk(n_live, torch.int32, "n_live", 1)
+    _chk(cand_s, torch.float32, "cand_s")
+    _chk(cand_i, torch.int32, "cand_i")
+    D = rows_u8.shape[1]
+    NQ = q_e4m3.shape[0]
+    n_valid, n_rblk, stride = int(n_valid), int(n_rblk), int(stride)
+    if D not in FILTER_FP8_DIMS or q_e4m3.shape[1] != D:
+        raise ValueError(f"index_scan_filter_group_fp8: rows must be {FILTER_FP8_DIMS} wide, "
+                         "queries alike")
+    if kmax not in (16, 32) or stride < 1 or n_rblk < 1:
+        raise ValueError("index_scan_filter_group_fp8: kmax in (16, 32), stride >= 1, n_rblk >= 1")
+    if mask8.shape[1] != MASK_GROUPS or not mask8.is_contiguous():
+        raise ValueError("index_scan_filter_group_fp8: mask8 must be contiguous "
+                         f"[n_words, {MASK_GROUPS}]")
+    if qgroup.numel() != NQ:
+        raise ValueError("index_scan_filter_group_fp8: qgroup must hold one group per query")
+    n_tiles = (n_valid + 63) // 64
+    # every tile the list can name lies inside the row slab and has its eight mask words
+    if (n_valid < 0 or n_tiles * 64 > rows_u8.shape[0] or n_tiles > mask8.shape[0]
+            or n_tiles > tiles.numel() or n_live.numel() < 1):
+        raise ValueError("index_scan_filter_group_fp8: rows / mask8 / tile list shorter than "
+                         "n_valid")
+    need = NQ * n_rblk * 2 * kmax
+    if cand_s.numel() < need or cand_i.numel() < need:
+        raise ValueError("index_scan_filter_group_fp8: candidate workspace too small")
+    if thr_init is not None:
+        _chk(thr_init, torch.float32, "thr_init", 1)
+        if thr_init.numel() < NQ:
+            raise ValueError("index_scan_filter_group_fp8: thr_init shorter than the batch")
+    if gate is not None:
+        _chk(gate, torch.int32, "gate", 1)
+        if gate.numel() < 1:
+            raise ValueError("index_scan_filter_group_fp8: gate is one int32 flag")
+    hip().index_scan_filter_group_fp8(_ptr(rows_u8), n_valid, D, _ptr(tiles), _ptr(n_live),
+                                      _ptr(mask8), _ptr(qgroup), stride, n_rblk, _ptr(q_e4m3), NQ,
+                                      kmax, _ptr(cand_s), _ptr(cand_i),
+                                      stream_handle(rows_u8.device), _ptr(thr_init), xcd,
+                                      _ptr(gate))
+
+
 def index_scan_emit_fp8(rows_u8: torch.Tensor, n_valid: int, mask_words: torch.Tensor,
                         tiles: torch.Tensor, n_live: torch.Tensor, q_e4m3: torch.Tensor,
                         thr: torch.Tensor, cand_s: torch.Tensor, cand_i: torch.Tensor,

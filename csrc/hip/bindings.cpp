@@ -99,6 +99,12 @@ int symb_index_scan_filter_fp8(const void* X, int n_valid, int D, const int* til
                                hipStream_t st, const float* thr_init, int xcd,
                                const int* gate = nullptr);
 int symb_filter_fp8_ring_depth(int D);
+// ... under a mask per query group (index_filter_group_fp8.hip)
+int symb_index_scan_filter_group_fp8(const void* X, int n_valid, int D, const int* tiles,
+                                     const int* n_live, const void* mask8, const int* qgroup,
+                                     int stride, int n_rblk, const void* Q, int NQ, int kmax,
+                                     float* cand_s, int* cand_i, hipStream_t st,
+                                     const float* thr_init, int xcd, const int* gate);
 // the masked emitting scan over e4m3 rows (index_emit_fp8.hip)
 int symb_index_scan_emit_fp8(const void* X, int n_valid, int D, const int* tiles,
                              const int* n_live, const void* mask, int n_rblk, const void* Q,
@@ -966,6 +972,20 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("X"), py::arg("n_valid"), py::arg("D"), py::arg("tiles"), py::arg("n_live"),
      py::arg("mask"), py::arg("stride"), py::arg("n_rblk"), py::arg("Q"), py::arg("NQ"),
      py::arg("kmax"), py::arg("cand_s"), py::arg("cand_i"), py::arg("stream"),
+     py::arg("thr_init") = 0, py::arg("xcd") = 1, py::arg("gate") = 0);
+  m.def("index_scan_filter_group_fp8", [](uptr X, int n_valid, int D, uptr tiles, uptr n_live,
+                                          uptr mask8, uptr qgroup, int stride, int n_rblk,
+                                          uptr Q, int NQ, int kmax, uptr cand_s, uptr cand_i,
+                                          uptr st, uptr thr, int xcd, uptr gate) {
+    check(symb_index_scan_filter_group_fp8(P<void>(X), n_valid, D, P<const int>(tiles),
+                                           P<const int>(n_live), P<void>(mask8),
+                                           P<const int>(qgroup), stride, n_rblk, P<void>(Q), NQ,
+                                           kmax, P<float>(cand_s), P<int>(cand_i), S(st),
+                                           P<const float>(thr), xcd, P<const int>(gate)),
+          "index_scan_filter_group_fp8");
+  }, py::arg("X"), py::arg("n_valid"), py::arg("D"), py::arg("tiles"), py::arg("n_live"),
+     py::arg("mask8"), py::arg("qgroup"), py::arg("stride"), py::arg("n_rblk"), py::arg("Q"),
+     py::arg("NQ"), py::arg("kmax"), py::arg("cand_s"), py::arg("cand_i"), py::arg("stream"),
      py::arg("thr_init") = 0, py::arg("xcd") = 1, py::arg("gate") = 0);
   m.def("index_scan_emit_fp8", [](uptr X, int n_valid, int D, uptr tiles, uptr n_live, uptr mask,
                                   int n_rblk, uptr Q, int NQ, uptr thr, uptr cand_s, uptr cand_i,

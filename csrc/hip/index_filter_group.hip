@@ -35,35 +35,13 @@
 // Register budget: three VGPRs more than index_scan_filter_kernel (the word pair and the group
 // id).  PF (fragment reads in flight) is that kernel's at every instantiation; none uses scratch
 // (profiles/r14_group_filter/resource_usage.md).
-#include "scan_common.h"
+// (MASK_GROUPS, sload_mask8, swait_mask8, pick_word: mask_group.h, shared with the fp8 form)
+#include "mask_group.h"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace symb {
-
-constexpr int MASK_GROUPS = 8;
-
-typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
-
-// the eight mask words of one tile, one hand-issued scalar load (as sload_u64, scan_common.h)
-__device__ __forceinline__ void sload_mask8(u32x16& dst, const uint64_t* p) {
-  asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(dst) : "s"(p));
-}
-// swait (scan_common.h) with the eight words in place of the one
-__device__ __forceinline__ void swait_mask8(int& a, int& b, u32x16& w) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a), "+s"(b), "+s"(w)::"memory");
-}
-// the word of group grp (0 .. 7, per lane) out of the eight wave-uniform ones
-__device__ __forceinline__ uint64_t pick_word(const u32x16& w, int grp) {
-  uint32_t lo = w[0], hi = w[1];
-#pragma unroll
-  for (int g = 1; g < MASK_GROUPS; ++g) {
-    lo = grp == g ? w[2 * g] : lo;
-    hi = grp == g ? w[2 * g + 1] : hi;
-  }
-  return ((uint64_t)hi << 32) | lo;
-}
 
 // Template parameters and tile / interval geometry as index_scan_filter_kernel.
 template <int D, bool MFMA_32, int KMAX, int NS, int AUX>

@@ -1,0 +1,693 @@
+"""The grouped masked e4m3 list scan (csrc/hip/index_filter_group_fp8.hip) and the search of a GPU
+fp8 shard under a mask per query built on it: against ops/reference.grouped_filtered_topk_ref over
+the DECODED rows and queries (the MFMA sums exact e4m3 products in fp32), and -- bit for bit in
+scores -- against the single-mask fp8 search (index_filter_fp8.hip) of each group's queries under
+that group's mask, which the existing tests pin to the oracle.
+
+Shapes are test_filter_fp8_gpu.py's and test_filter_group_gpu.py's: 64 * 37 + 19 rows (a partial
+last tile, few workgroups) and 20 011 rows (several workgroups, slices longer than the ring).
+Tolerances are test_filter_fp8_gpu.py's for this product (scores and returned rows' true scores
+atol 2e-3 against the fp32 oracle on decoded operands); the conditions on WHICH rows may come back
+carry none.  A lane of the fp8 kernel holds two queries, i and i + 32, so the assignments of
+queries to groups put those two in different groups at every lane, in the same group, and
+interleaved."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from codename_symbiont_amd.ops import reference as R
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+N_SMALL = 64 * 37 + 19
+N_BIG = 20_011
+DIMS = (256, 384, 512, 768, 1024)
+CASES = [(D, k, nq) for D in DIMS for k, nq in ((10, 1), (10, 300), (32, 130))]
+# query i -> group, for G groups: round 14's interleaved form; the two queries of every lane
+# (i, i + 32) in different groups; the two in the same group
+ASSIGN = {
+    "interleaved": lambda i, G: (i * 3 + i // 7) % G,
+    "lane pairs apart": lambda i, G: (i // 32) % G,
+    "lane pairs together": lambda i, G: (i // 64) % G,
+}
+
+_shards = {}
+
+
+def _shard(D, n):
+    """One random fp8 shard per (width, rows) for the whole module (never written after this),
+    with its decoded rows."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    key = (D, n)
+    if key not in _shards:
+        sh = HbmIndexShard(D, n + 100, device=DEV, dtype="fp8")
+        sh.fill_random(n, seed=5 + D + n)
+        _shards[key] = (sh, sh.unit_rows()[:n])
+    return _shards[key]
+
+
+def _queries(nq, D, seed=11):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return torch.nn.functional.normalize(torch.randn(nq, D, generator=g), dim=-1).bfloat16().to(DEV)
+
+
+def _decoded(q):
+    """The queries the fp8 scan scores: e4m3(FP8_SCALE * q), decoded."""
+    from codename_symbiont_amd.ops import kernels as K
+
+    return K.fp8_to_float(K.quant_fp8(q))
+
+
+def _tiles_mask(n, tiles):
+    a = torch.zeros(n, dtype=torch.bool)
+    for t in tiles:
+        a[t * 64:(t + 1) * 64] = True
+    return a
+
+
+def _rows_mask(n, idx):
+    return torch.zeros(n, dtype=torch.bool).index_fill_(0, torch.as_tensor(list(idx)), True)
+
+
+def _mixes(n, k):
+    """name -> (list of bool [n] masks on the host, random?): test_filter_group_gpu.py's ten."""
+    nt = (n + 63) // 64
+    rng = np.random.default_rng(n + k)
+    ones, zero = torch.ones(n, dtype=torch.bool), torch.zeros(n, dtype=torch.bool)
+    uni = lambda share: torch.from_numpy(rng.random(n) < share)
+    last = list(range((nt - 1) * 64, n))
+    half = _tiles_mask(n, [5])
+    half[5 * 64 + 32:] = False
+    return {
+        "ones next to zero": ([ones, zero], False),
+        "eight documents": ([_tiles_mask(n, range(g, nt, 8)) for g in range(8)], False),
+        "k-1 rows, none, half": ([_rows_mask(n, rng.choice(n, k - 1, replace=False)), zero,
+                                  uni(0.5)], False),
+        "one bit per tile": ([_rows_mask(n, [r for r in (t * 64 + (t * 7 + g * 13) % 64
+                                                         for t in range(nt)) if r < n])
+                              for g in range(4)], False),
+        "partial last tile only": ([_rows_mask(n, last), _rows_mask(n, last[::2]),
+                                    _rows_mask(n, last[-1:])], False),
+        "union of 1 live tile": ([half, _tiles_mask(n, [5]) & ~half, _tiles_mask(n, [5])], False),
+        "union of 2 live tiles": ([_tiles_mask(n, [5]), _tiles_mask(n, [nt - 2])], False),
+        "union of 3 live tiles": ([_tiles_mask(n, [0]), _tiles_mask(n, [9]), _tiles_mask(n, [20]),
+                                   _tiles_mask(n, [0, 20])], False),
+        "uniform 50% x 8": ([uni(0.5) for _ in range(8)], True),
+        "must_not 1% x 5": ([~_tiles_mask(n, range(g, nt, 100)) for g in range(5)], True),
+    }
+
+
+def _close(out, ref, atol, what):
+    err = (out.float() - ref.float()).abs()
+    bad = int((err > atol).sum())
+    assert bad == 0, f"{what}: {bad} elems off, max err {float(err.max()):.4g}"
+
+
+def _same(sh, q, s, r, s1, r1, what):
+    """Scores bit for bit; rows too, outside runs of equal scores.  Exact ties are common among
+    sums of e4m3 products, and a run can go on past k, where no equal neighbour shows it: a LAST
+    slot whose rows differ without an equal neighbour must be proved a tie -- neither row is among
+    the other side's rows, and the two rows, searched alone under a two-row mask (the single-mask
+    kernel, the same per-row MFMA chain), score the same bit for bit, which is the slot's score."""
+    assert torch.equal(s, s1), f"{what}: scores differ"
+    rr, gg = r.long(), r1.long()
+    tie = torch.zeros_like(rr, dtype=torch.bool)
+    if s.shape[1] > 1:
+        tie[:, 1:] |= s[:, 1:] == s[:, :-1]
+        tie[:, :-1] |= s[:, :-1] == s[:, 1:]
+    diff = (rr != gg) & ~tie
+    assert not bool(diff[:, :-1].any()), f"{what}: rows differ outside ties"
+    for i in torch.nonzero(diff[:, -1]).flatten().tolist():
+        a, b = int(rr[i, -1]), int(gg[i, -1])
+        assert a >= 0 and b >= 0, f"{what}: query {i}, last slot {a} against {b}"
+        assert b not in rr[i].tolist() and a not in gg[i].tolist(), f"{what}: query {i}"
+        s2, r2 = sh.search(q[i:i + 1], 2, allow=[a, b])
+        assert sorted(r2[0].tolist()) == sorted((a, b)), f"{what}: query {i}"
+        assert float(s2[0, 0]) == float(s2[0, 1]) == float(s[i, -1]), \
+            f"{what}: query {i}: last slot {a} against {b} is no tie"
+
+
+def _check_out(s, r, rows, qd, k, allows_d, group_of, what, random_mask=False):
+    """(scores, rows) of one grouped search against the oracle over the decoded rows [n, D] and
+    decoded queries: the hard conditions of test_filter_group_gpu._check and the tolerances of
+    test_filter_fp8_gpu.py."""
+    n, nq = rows.shape[0], qd.shape[0]
+    ref_s, ref_i = R.grouped_filtered_topk_ref(rows, qd, k, allows_d, group_of)
+    torch.cuda.synchronize()
+    assert s.shape == (nq, k) and r.shape == (nq, k), what
+    assert s.dtype == torch.float32 and r.dtype == torch.int32, what
+    fin = torch.isfinite(ref_s)
+    g_d = torch.tensor(group_of, device=DEV)
+    cnt = torch.stack(allows_d).sum(1)[g_d].clamp_max(k)
+    assert torch.equal(fin.sum(1), cnt), what
+    # the (-inf, -1) tail is exactly where the oracle has it
+    assert torch.equal(torch.isfinite(s), fin), what
+    assert bool((s[~fin] == -math.inf).all()) and bool((r[~fin] == -1).all()), what
+    rr = r.long()
+    # hard conditions: rows the query's OWN mask allows, none at or past `visible`, none twice
+    assert bool((rr[fin] >= 0).all()) and bool((rr[fin] < n).all()), what
+    own = torch.stack(allows_d)[g_d[:, None].expand_as(rr), rr.clamp_min(0)]
+    assert bool(own[fin].all()), f"{what}: a row another query's mask allows came back"
+    srt = torch.sort(torch.where(fin, rr, torch.arange(-k, 0, device=DEV).expand_as(rr)), 1).values
+    assert bool((srt[:, 1:] != srt[:, :-1]).all()), f"{what}: a row came back twice"
+    _close(s[fin], ref_s[fin], 2e-3, f"{what}: scores")
+    true = R.row_scores_ref(rows, qd, rr.clamp_min(0))
+    _close(s[fin], true[fin], 2e-3, f"{what}: returned rows' true scores")
+
+
+def _check(sh, rows, q, qd, k, allows, group_of, what, random_mask=False, per_group=True):
+    """One grouped search through the shard against the oracle and, per group, against the
+    single-mask search of that group's queries; returns (scores, rows)."""
+    nq = q.shape[0]
+    allows_d = [a.to(DEV) for a in allows]
+    mg = sh.make_mask_groups(allows_d, group_of)
+    s, r = sh.search(q, k, allow=mg)
+    _check_out(s, r, rows, qd, k, allows_d, group_of, what, random_mask)
+    if per_group:
+        # same row, same score: each group's queries under the single-mask search
+        for g, a in enumerate(allows_d):
+            idx = [i for i in range(nq) if group_of[i] == g]
+            if idx:
+                sg, rg = sh.search(q[idx], k, allow=a)
+                _same(sh, q[idx], s[idx], r[idx], sg, rg, f"{what}: group {g}")
+    return s, r
+
+
+def _words(allow):
+    """bool [n] on the host -> packed int64 words on the device."""
+    n = allow.numel()
+    b = np.zeros((n + 63) // 64 * 8, dtype=np.uint8)
+    p = np.packbits(allow.numpy(), bitorder="little")
+    b[:p.size] = p
+    return torch.from_numpy(b).to(DEV).view(torch.int64)
+
+
+def _mask8(allows, slots=None):
+    """bool [n] masks on the host -> int64 [n_words, 8] on the device, mask j in slot slots[j]."""
+    w = [_words(a) for a in allows]
+    m8 = torch.zeros(w[0].numel(), 8, dtype=torch.int64, device=DEV)
+    for j, x in enumerate(w):
+        m8[:, j if slots is None else slots[j]] = x
+    return m8
+
+
+def _raw_search(sh, n, mask8, qgroup, tiles, n_live, q8, k, kmax, n_rblk, stride=1, thr=None):
+    """index_scan_filter_group_fp8 + topk_merge; raw scores rescaled."""
+    from codename_symbiont_amd.ops import kernels as K
+    from codename_symbiont_amd.ops._ext import hip, stream_handle
+
+    nq = q8.shape[0]
+    cs = torch.empty(nq, n_rblk * 2 * kmax, device=DEV)
+    ci = torch.empty(nq, n_rblk * 2 * kmax, dtype=torch.int32, device=DEV)
+    K.index_scan_filter_group_fp8(sh.rows, n, mask8, qgroup, tiles, n_live, q8, kmax, n_rblk, cs,
+                                  ci, thr_init=thr, stride=stride)
+    out_s = torch.empty(nq, k, device=DEV)
+    out_i = torch.empty(nq, k, dtype=torch.int32, device=DEV)
+    hip().topk_merge(cs.data_ptr(), ci.data_ptr(), nq, cs.shape[1], kmax, k, out_s.data_ptr(),
+                     out_i.data_ptr(), 0, 0, stream_handle(sh.device), 0)
+    return out_s * (1.0 / (K.FP8_SCALE * K.FP8_SCALE)), out_i
+
+
+# 1 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D,k,nq", CASES)
+def test_grouped_fp8_search_mixes(D, k, nq):
+    """Every group mix under every assignment of queries to groups against the oracle and, per
+    group, the single-mask search bit for bit (all five widths, both kmax).  (nq = 1 names one
+    group: the single-mask route.)"""
+    q = _queries(nq, D)
+    qd = _decoded(q)
+    for n in (N_SMALL, N_BIG):
+        sh, rows = _shard(D, n)
+        for name, (allows, rnd) in _mixes(n, k).items():
+            G = len(allows)
+            for aname, f in ASSIGN.items():
+                if nq == 1 and aname != "interleaved":
+                    continue                              # (one query: the same search again)
+                group_of = [f(i, G) for i in range(nq)]
+                _check(sh, rows, q, qd, k, allows, group_of,
+                       f"D={D} n={n} k={k} nq={nq} {name}, {aname}", rnd)
+
+
+# 2 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", DIMS)
+def test_slices_around_the_ring_depth(D):
+    """Unions of NS - 1, NS, NS + 1 and 2 NS + 1 live tiles spread over the shard and split over
+    two or three groups, in one slice and in three, every entry and every second one, both kmax
+    (kmax = 32 loads the mask words at another point of the interval): slices shorter than the
+    ring, as long as it and longer, and the clamped re-loads at their tails.  At 768 a list
+    entry is two intervals.  With a stride the kernel walks every stride-th entry of each
+    workgroup's slice of the UNION's list, so a group's reference mask is its allowed rows in
+    exactly those tiles."""
+    from codename_symbiont_amd.ops import kernels as K
+    from codename_symbiont_amd.ops._ext import hip
+
+    n, k, nq = N_SMALL, 10, 70
+    nt = (n + 63) // 64
+    sh, rows = _shard(D, n)
+    q = _queries(nq, D, seed=51)
+    q8 = K.quant_fp8(q)
+    qd = K.fp8_to_float(q8)
+    rng = np.random.default_rng(D)
+    ns = hip().filter_fp8_ring_depth(D)        # the ring depth both masked fp8 scans are built with
+    assert 2 <= ns <= 8
+    for m in (ns - 1, ns, ns + 1, 2 * ns + 1):
+        live = sorted({int(round(t)) for t in np.linspace(0, nt - 1, m)})
+        assert len(live) == m
+        G = 2 + m % 2
+        allows = [torch.zeros(n, dtype=torch.bool) for _ in range(G)]
+        for j, t in enumerate(live):
+            # tile j belongs to group j % G (a random half of it, never empty); every third tile
+            # also to the next group, so the groups' tile sets overlap without being equal
+            lo, hi = t * 64, min(n, t * 64 + 64)
+            for g in {j % G, (j + 1) % G if j % 3 == 0 else j % G}:
+                allows[g][lo:hi] = torch.from_numpy(rng.random(hi - lo) < 0.5)
+                allows[g][lo + g] = True
+        mask8 = _mask8(allows)
+        union = allows[0].clone()
+        for a in allows[1:]:
+            union |= a
+        tiles, n_live = K.filter_tiles(_words(union), n)
+        assert int(n_live) == m
+        group_of = [(i // 32) % G for i in range(nq)]
+        qgroup = torch.tensor(group_of, dtype=torch.int32, device=DEV)
+        for n_rblk in (1, 3):
+            per = -(-m // n_rblk)
+            for stride in (1, 2):
+                walked = _tiles_mask(n, [t for rb in range(n_rblk)
+                                         for t in live[rb * per:(rb + 1) * per][::stride]])
+                want = [(a & walked).to(DEV) for a in allows]
+                for kmax in (16, 32):
+                    what = f"D={D} live={m} n_rblk={n_rblk} stride={stride} kmax={kmax}"
+                    s, r = _raw_search(sh, n, mask8, qgroup, tiles, n_live, q8, k, kmax, n_rblk,
+                                       stride)
+                    _check_out(s, r, rows, qd, k, want, group_of, what)
+
+
+# 3 ------------------------------------------------------------------------------------------------
+def test_raw_wrapper_on_dirty_input():
+    """The kernel on words whose bits at and past `visible` are set (in the last tile and in words
+    past it), with e4m3 copies of the queries in the slab's rows past `visible` (a scan that
+    ignored n_valid would return them at ~1.0), qgroup entries of 8 + g, the unused slots zero
+    and the tile list filled past n_live (with an in-range tile, so nothing can fault); a closed
+    gate; and thr_init."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+    from codename_symbiont_amd.ops import kernels as K
+    from codename_symbiont_amd.ops._ext import hip, stream_handle
+
+    D, n, k, nq, kmax = 384, N_SMALL, 10, 70, 16
+    sh = HbmIndexShard(D, n + 200, device=DEV, dtype="fp8")
+    sh.fill_random(n, seed=3)
+    rows = sh.unit_rows()[:n]
+    q = _queries(nq, D)
+    q8 = K.quant_fp8(q)
+    qd = K.fp8_to_float(q8)
+    sh.rows[n:n + nq].copy_(q8)                     # unpublished rows of the last tile and beyond
+    rng = np.random.default_rng(4)
+    slots = (0, 2, 7)
+    allows = [torch.from_numpy(rng.random(n) < share) for share in (0.2, 0.5, 0.03)]
+    group_of = [(i // 32 + i) % 3 for i in range(nq)]
+    s0, r0 = _check(sh, rows, q, qd, k, allows, group_of, "bool masks")
+    nw = (n + 63) // 64
+    mask8 = torch.zeros(nw + 2, 8, dtype=torch.int64, device=DEV)
+    mask8[:nw] = _mask8(allows, slots)
+    for g in slots:                                 # dirty: every bit at and past n, words past it
+        mask8[n // 64, g] |= -1 << (n % 64)
+        mask8[nw:, g] = -1
+    union = (mask8[:nw, 0] | mask8[:nw, 2] | mask8[:nw, 7]).contiguous()
+    tiles, n_live = K.filter_tiles(union, n)
+    tiles[int(n_live):] = 3                         # past n_live: in range, but not the list's
+    # every other query names its slot as 8 + slot: only the low three bits count
+    qgroup = torch.tensor([slots[g] + (8 if i % 2 else 0) for i, g in enumerate(group_of)],
+                          dtype=torch.int32, device=DEV)
+    n_rblk = 5
+    cs = torch.full((nq, n_rblk * 2 * kmax), 123.0, device=DEV)
+    ci = torch.full((nq, n_rblk * 2 * kmax), -7, dtype=torch.int32, device=DEV)
+    gate = torch.zeros(1, dtype=torch.int32, device=DEV)
+    K.index_scan_filter_group_fp8(sh.rows, n, mask8, qgroup, tiles, n_live, q8, kmax, n_rblk, cs,
+                                  ci, gate=gate)
+    torch.cuda.synchronize()
+    assert bool((cs == 123.0).all()) and bool((ci == -7).all())     # closed gate: untouched
+    gate.fill_(1)
+    K.index_scan_filter_group_fp8(sh.rows, n, mask8, qgroup, tiles, n_live, q8, kmax, n_rblk, cs,
+                                  ci, gate=gate)
+    raw_s = torch.empty(nq, k, device=DEV)
+    out_i = torch.empty(nq, k, dtype=torch.int32, device=DEV)
+    hip().topk_merge(cs.data_ptr(), ci.data_ptr(), nq, cs.shape[1], kmax, k, raw_s.data_ptr(),
+                     out_i.data_ptr(), 0, 0, stream_handle(sh.device), 0)
+    out_s = raw_s * (1.0 / (K.FP8_SCALE * K.FP8_SCALE))
+    torch.cuda.synchronize()
+    assert int(out_i.max()) < n
+    _check_out(out_s, out_i, rows, qd, k, [a.to(DEV) for a in allows], group_of, "raw kernels")
+    _same(sh, q, out_s, out_i, s0, r0, "raw kernels against the shard")
+    # thr_init (raw units): each query's 5th best score -> nothing at or below it comes back,
+    # everything above it does
+    thr = raw_s[:, 4].contiguous()
+    assert bool(torch.isfinite(thr).all())
+    s1, r1 = _raw_search(sh, n, mask8, qgroup, tiles, n_live, q8, k, kmax, n_rblk, thr=thr)
+    torch.cuda.synchronize()
+    raw1 = s1 * (K.FP8_SCALE * K.FP8_SCALE)
+    fin = torch.isfinite(s1)
+    assert bool((raw1[fin] > thr[:, None].expand_as(raw1)[fin]).all())
+    assert torch.equal(fin.sum(1), (raw_s > thr[:, None]).sum(1))
+    assert bool((r1[~fin] == -1).all())
+    above = raw_s > thr[:, None]
+    assert torch.equal(s1[above], out_s[above])
+
+
+# 4 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D,k", [(384, 10), (768, 10), (1024, 32), (256, 32)])
+def test_seed_pass_on_and_off_identical(D, k):
+    nq = 130
+    sh, _ = _shard(D, N_BIG)
+    q = _queries(nq, D, seed=41)
+    mixes = _mixes(N_BIG, k)
+    try:
+        for name in ("ones next to zero", "eight documents", "uniform 50% x 8",
+                     "union of 3 live tiles"):
+            allows = [a.to(DEV) for a in mixes[name][0]]
+            mg = sh.make_mask_groups(allows, [(i // 32) % len(allows) for i in range(nq)])
+            sh.filter_seed = True
+            s1, r1 = sh.search(q, k, allow=mg)
+            sh.filter_seed = False
+            s0, r0 = sh.search(q, k, allow=mg)
+            torch.cuda.synchronize()
+            assert torch.equal(s0, s1) and torch.equal(r0, r1), name
+    finally:
+        sh.filter_seed = type(sh).FILTER_SEED_DEFAULT
+
+
+def _count_scans(monkeypatch):
+    from codename_symbiont_amd.ops import kernels as K
+
+    calls = []
+    real = K.index_scan_filter_group_fp8
+    monkeypatch.setattr(K, "index_scan_filter_group_fp8",
+                        lambda *a, **kw: (calls.append(a[6].shape[0]), real(*a, **kw))[1])
+    return calls
+
+
+# 5 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("G,scans", [(9, 2), (17, 3)])
+def test_chunks_of_eight_masks(G, scans, monkeypatch):
+    D, n, k, nq = 384, N_SMALL, 10, 60
+    sh, rows = _shard(D, n)
+    q = _queries(nq, D, seed=51)
+    qd = _decoded(q)
+    rng = np.random.default_rng(G)
+    allows = [torch.from_numpy(rng.random(n) < 0.3) for _ in range(G)]
+    group_of = [(i * 5) % G for i in range(nq)]
+    calls = _count_scans(monkeypatch)
+    sh.filter_seed = False
+    try:
+        _check(sh, rows, q, qd, k, allows, group_of, f"{G} masks", True, per_group=False)
+    finally:
+        sh.filter_seed = type(sh).FILTER_SEED_DEFAULT
+    assert len(calls) == scans and sum(calls) == nq
+    _check(sh, rows, q, qd, k, allows, group_of, f"{G} masks, seeded", True)
+
+
+def _bar(monkeypatch, *names):
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    for name in names:
+        def barred(self, *a, _name=name, **kw):
+            raise AssertionError(f"the search took {_name}")
+        monkeypatch.setattr(HbmIndexShard, name, barred)
+
+
+# 6 ------------------------------------------------------------------------------------------------
+def test_all_queries_in_one_group_is_the_ungrouped_search(monkeypatch):
+    """One distinct mask (given once, or twice as equal masks): the single-mask search, and the
+    grouped wrapper never runs.  And the kernel itself with every query in slot 3: the
+    single-mask kernel's candidates, bit for bit."""
+    from codename_symbiont_amd.ops import kernels as K
+
+    D, n, k, nq = 768, N_BIG, 10, 130
+    sh, _ = _shard(D, n)
+    q = _queries(nq, D, seed=52)
+    a = torch.from_numpy(np.random.default_rng(53).random(n) < 0.2).to(DEV)
+    s0, r0 = sh.search(q, k, allow=a)
+    with monkeypatch.context() as m:
+        def barred(*a, **kw):
+            raise AssertionError("the search took the grouped scan")
+        m.setattr(K, "index_scan_filter_group_fp8", barred)
+        for masks, group_of in (([a], [0] * nq), ([a, a.clone()], [i % 2 for i in range(nq)])):
+            mg = sh.make_mask_groups(masks, group_of)
+            assert len(mg) == 1
+            s, r = sh.search(q, k, allow=mg)
+            assert torch.equal(s, s0) and torch.equal(r, r0)
+    mask = sh.make_mask(a)
+    q8 = K.quant_fp8(q)
+    n_rblk = 7
+    for kmax in (16, 32):
+        shape = (nq, n_rblk * 2 * kmax)
+        cs0, ci0 = torch.empty(shape, device=DEV), torch.empty(shape, dtype=torch.int32, device=DEV)
+        cs1, ci1 = torch.empty(shape, device=DEV), torch.empty(shape, dtype=torch.int32, device=DEV)
+        K.index_scan_filter_fp8(sh.rows, n, mask.words, mask.tiles, mask.n_live, q8, kmax, n_rblk,
+                                cs0, ci0)
+        mask8 = torch.zeros(mask.words.numel(), 8, dtype=torch.int64, device=DEV)
+        mask8[:, 3] = mask.words
+        qgroup = torch.full((nq,), 3, dtype=torch.int32, device=DEV)
+        K.index_scan_filter_group_fp8(sh.rows, n, mask8, qgroup, mask.tiles, mask.n_live, q8, kmax,
+                                      n_rblk, cs1, ci1)
+        torch.cuda.synchronize()
+        assert torch.equal(cs0, cs1) and torch.equal(ci0, ci1), kmax
+
+
+# 7 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", [384, 1024])
+def test_route_is_the_grouped_scan_up_to_k_32(D, monkeypatch):
+    """A grouped fp8 search at k = 10 and k = 32 runs with the single-mask search and the matmul
+    barred: neither the per-mask loop nor a fallback serves it.  At k = 40 the loop still does."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    n, nq = N_BIG, 70
+    sh, rows = _shard(D, n)
+    q = _queries(nq, D, seed=81)
+    qd = _decoded(q)
+    rng = np.random.default_rng(82)
+    allows = [torch.from_numpy(rng.random(n) < 0.3) for _ in range(3)]
+    allows_d = [a.to(DEV) for a in allows]
+    group_of = [(i // 32) % 3 for i in range(nq)]
+    mg = sh.make_mask_groups(allows_d, group_of)
+    for k in (10, 32):
+        with monkeypatch.context() as m:
+            _bar(m, "_search_masked", "_search_matmul")
+            calls = _count_scans(m)
+            s, r = sh.search(q, k, allow=mg)
+            assert len(calls) == 2 and calls[0] == nq         # seed pass + full pass, one chunk
+        _check_out(s, r, rows, qd, k, allows_d, group_of, f"D={D} k={k}", True)
+    took = []
+    real = HbmIndexShard._search_masked
+    monkeypatch.setattr(HbmIndexShard, "_search_masked",
+                        lambda self, *a, **kw: (took.append(1), real(self, *a, **kw))[1])
+    calls = _count_scans(monkeypatch)
+    s, r = sh.search(q, 40, allow=mg)
+    assert len(took) == 3 and calls == []
+    assert s.shape == (nq, 40) and bool(torch.isfinite(s).all())
+    own = torch.stack(allows_d)[torch.tensor(group_of, device=DEV)[:, None].expand_as(r), r.long()]
+    assert bool(own.all())
+
+
+# 8 ------------------------------------------------------------------------------------------------
+def test_tombstones_under_grouped_masks():
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+    from codename_symbiont_amd.ops import kernels as K
+
+    D, n, k, nq = 512, N_SMALL, 10, 70
+    sh = HbmIndexShard(D, n + 100, device=DEV, dtype="fp8")
+    sh.fill_random(n, seed=61)
+    q = _queries(nq, D, seed=62)
+    qd = _decoded(q)
+    rng = np.random.default_rng(63)
+    allows = [torch.from_numpy(rng.random(n) < 0.5) for _ in range(3)]
+    group_of = [(i // 32) % 3 for i in range(nq)]
+    mg = sh.make_mask_groups([a.to(DEV) for a in allows], group_of)
+    s, r = sh.search(q, k, allow=mg)
+    inside = torch.unique(r[:, :3].long().flatten())        # the best rows of every query
+    outside = torch.nonzero(~(allows[0] | allows[1] | allows[2])).flatten()[:20].to(DEV)
+    assert outside.numel() > 0
+    dead = torch.cat([inside, outside])
+    sh.delete_rows(dead.tolist())
+    with pytest.raises(ValueError, match="before a delete"):
+        sh.search(q, k, allow=mg)
+    with pytest.raises(ValueError, match="before a delete"):
+        sh.make_mask_groups(mg.masks, group_of)
+    alive = torch.ones(n, dtype=torch.bool)
+    alive[dead.cpu()] = False
+    # masks made now pass no dead row: the oracle under allow & alive, per group bit for bit
+    mg2 = sh.make_mask_groups([a.to(DEV) for a in allows], group_of)
+    s2, r2 = sh.search(q, k, allow=mg2)
+    assert not bool(torch.isin(r2.long(), dead).any())
+    _check_out(s2, r2, sh.unit_rows()[:n], qd, k, [(a & alive).to(DEV) for a in allows], group_of,
+               "after the delete")
+    for g, a in enumerate(allows):
+        idx = [i for i in range(nq) if group_of[i] == g]
+        sg, rg = sh.search(q[idx], k, allow=a.to(DEV))
+        _same(sh, q[idx], s2[idx], r2[idx], sg, rg, f"after the delete: group {g}")
+
+
+# 9 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pipeline", ["0", "1"])
+def test_vector_store_fp8_filter_list(pipeline, monkeypatch):
+    from codename_symbiont_amd.index.filter import Filter
+    from codename_symbiont_amd.index.shard import Payload
+    from codename_symbiont_amd.index.store import VectorStore
+
+    monkeypatch.setenv("SYMB_SEARCH_PIPELINE", pipeline)
+    D, k = 384, 10
+    st = VectorStore(D, 4096, device="cuda", dtype="fp8")
+    assert (st._streams is not None) == (pipeline == "1")
+    sizes = {"doc-a": 5, "doc-b": 40, "doc-c": 300, "doc-d": 700}
+    rng = np.random.default_rng(12)
+    ids, pls = [], []
+    for doc, m in sizes.items():
+        for j in range(m):
+            ids.append(f"{doc}/{j}")
+            pls.append(Payload(doc, f"http://{doc}.example", f"s{j}", j, "m", 0))
+    order = rng.permutation(len(ids))                  # documents interleaved over the rows
+    ids, pls = [ids[i] for i in order], [pls[i] for i in order]
+    st.upsert(ids, rng.standard_normal((len(ids), D)).astype(np.float32), pls)
+    only = lambda doc: Filter(must={"original_document_id": doc})
+    but = lambda doc: Filter(must_not={"original_document_id": doc})
+    flts = [only("doc-a"), None, but("doc-d"), only("doc-c"), but("doc-c"), None, only("doc-a"),
+            but("doc-d"), Filter(point_ids=["doc-b/1", "doc-d/2"]), only("doc-b"), but("doc-a")]
+    q = rng.standard_normal((len(flts), D)).astype(np.float32)
+    s, r = st.search(q, k, filter=flts)
+    assert s.shape == (len(flts), k) and r.shape == (len(flts), k)
+    for i, f in enumerate(flts):
+        si, ri = st.search(q[i], k, filter=f)
+        fin = np.isfinite(si[0])
+        assert np.array_equal(np.isfinite(s[i]), fin) and (r[i][~fin] == -1).all(), i
+        if f is not None:
+            # the single-mask scan of this request alone: the same bits
+            assert np.array_equal(s[i], si[0]), i
+        else:
+            # (an unfiltered search picks its route by the batch: the standing tolerance)
+            assert np.allclose(s[i][fin], si[0][fin], rtol=0, atol=2e-3), i
+        tie = np.zeros(k, bool)
+        tie[1:] |= si[0][1:] == si[0][:-1]
+        tie[:-1] |= si[0][:-1] == si[0][1:]
+        tie[-1] |= bool(fin[-1])          # (a run of equal scores can go on past k)
+        assert ((r[i] == ri[0]) | tie | (f is None)).all(), i
+    # the None entries are the plain search of those queries, bit for bit
+    plain = [i for i, f in enumerate(flts) if f is None]
+    sp, rp = st.search(q[plain], k)
+    assert np.array_equal(s[plain], sp) and np.array_equal(r[plain], rp)
+    assert int(np.isfinite(s[0]).sum()) == 5 and int(np.isfinite(s[8]).sum()) == 2
+    assert {st.lookup(int(g))[0] for g in r[8][:2]} == {"doc-b/1", "doc-d/2"}
+    # the route really taken: no filtered entry goes through a single-mask search or the matmul
+    rest = [i for i, f in enumerate(flts) if f is not None]
+    with monkeypatch.context() as m:
+        _bar(m, "_search_masked", "_search_matmul")
+        calls = _count_scans(m)
+        s2, r2 = st.search(q[rest], k, filter=[flts[i] for i in rest])
+        assert len(calls) == 2 and calls[0] == len(rest)      # seed pass + full pass, one chunk
+    assert np.array_equal(s2, s[rest]) and np.array_equal(r2, r[rest])
+
+
+# 10 -----------------------------------------------------------------------------------------------
+def test_wrapper_validation_errors(monkeypatch):
+    from codename_symbiont_amd.ops import kernels as K
+    from codename_symbiont_amd.ops import _ext
+
+    assert hasattr(_ext.hip(), "index_scan_filter_group_fp8")
+    D, n, nq, kmax, n_rblk = 384, N_SMALL, 7, 16, 2
+    sh, _ = _shard(D, n)
+    q = _queries(nq, D)
+    q8 = K.quant_fp8(q)
+    nw = (n + 63) // 64
+    mask8 = torch.zeros(nw, 8, dtype=torch.int64, device=DEV)
+    qgroup = torch.zeros(nq, dtype=torch.int32, device=DEV)
+    tiles, n_live = K.filter_tiles(mask8[:, 0].contiguous(), n)
+    cs = torch.empty(nq, n_rblk * 2 * kmax, device=DEV)
+    ci = torch.empty(nq, n_rblk * 2 * kmax, dtype=torch.int32, device=DEV)
+    launched = []
+    real = _ext.hip().index_scan_filter_group_fp8
+
+    class Spy:
+        def __getattr__(self, name):
+            if name == "index_scan_filter_group_fp8":
+                return lambda *a, **kw: launched.append(1) or real(*a, **kw)
+            return getattr(_ext.hip(), name)
+
+    spy = Spy()
+    monkeypatch.setattr(K, "hip", lambda: spy)
+
+    def call(rows=sh.rows, n_valid=n, m8=mask8, qg=qgroup, tl=tiles, nl=n_live, qq=q8, kmax=kmax,
+             n_rblk=n_rblk, cs=cs, ci=ci, **kw):
+        K.index_scan_filter_group_fp8(rows, n_valid, m8, qg, tl, nl, qq, kmax, n_rblk, cs, ci, **kw)
+
+    wide = torch.zeros(n + 100, 320, dtype=torch.uint8, device=DEV)
+    for what, exc, kw in (
+            ("bf16 rows", ValueError, dict(rows=torch.zeros(n + 100, D, dtype=torch.bfloat16,
+                                                            device=DEV))),
+            ("bf16 queries", ValueError, dict(qq=q)),
+            ("wrong width", ValueError, dict(rows=wide, qq=torch.zeros(nq, 320, dtype=torch.uint8,
+                                                                      device=DEV))),
+            ("query width", ValueError, dict(qq=torch.zeros(nq, 256, dtype=torch.uint8,
+                                                            device=DEV))),
+            ("int32 mask8", TypeError, dict(m8=mask8.to(torch.int32))),
+            ("int64 qgroup", TypeError, dict(qg=qgroup.long())),
+            ("four slots", ValueError, dict(m8=torch.zeros(nw, 4, dtype=torch.int64, device=DEV))),
+            ("single-mask layout", ValueError, dict(m8=mask8[:, 0].contiguous())),
+            ("mask8 not contiguous", ValueError,
+             dict(m8=torch.zeros(8, nw, dtype=torch.int64, device=DEV).t())),
+            ("short mask8", ValueError, dict(m8=mask8[:nw - 1])),
+            ("short tile list", ValueError, dict(tl=tiles[:-1])),
+            ("short slab", ValueError, dict(rows=sh.rows[:n])),
+            ("n_valid past the slab", ValueError, dict(n_valid=sh.rows.shape[0] + 64)),
+            ("short qgroup", ValueError, dict(qg=qgroup[:nq - 1])),
+            ("long qgroup", ValueError, dict(qg=torch.zeros(nq + 1, dtype=torch.int32,
+                                                            device=DEV))),
+            ("host qgroup", ValueError, dict(qg=qgroup.cpu())),
+            ("kmax 8", ValueError, dict(kmax=8)),
+            ("stride 0", ValueError, dict(stride=0)),
+            ("n_rblk 0", ValueError, dict(n_rblk=0)),
+            ("small workspace", ValueError, dict(n_rblk=3)),
+            ("short thr_init", ValueError, dict(thr_init=torch.zeros(nq - 1, device=DEV))),
+            ("2-d thr_init", ValueError, dict(thr_init=torch.zeros(nq, 1, device=DEV))),
+            ("int64 gate", TypeError, dict(gate=torch.zeros(1, dtype=torch.int64, device=DEV))),
+            ("2-d gate", ValueError, dict(gate=torch.zeros(1, 1, dtype=torch.int32, device=DEV)))):
+        with pytest.raises(exc):
+            call(**kw)
+        assert not launched, what
+    call()                                              # the baseline is accepted
+    torch.cuda.synchronize()
+    assert launched == [1]
+
+
+# 11 -----------------------------------------------------------------------------------------------
+def test_disjoint_masks_over_an_extra_query_block_keep_the_loop(monkeypatch):
+    """The route condition on fp8 (_loop_keeps_chunk at 256 queries per block): two disjoint masks
+    whose groups fit one query block each but need two together stay with the per-mask loop once
+    the union has GROUP_LOOP_MIN_TILES tiles; at 256 queries or fewer, and under overlapping
+    masks, the grouped scan runs.  Both routes give the same bits."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    D, n, k, nq = 512, N_BIG, 10, 300
+    sh, rows = _shard(D, n)
+    q = _queries(nq, D, seed=71)
+    qd = _decoded(q)
+    nt = (n + 63) // 64
+    even, odd = _tiles_mask(n, range(0, nt, 2)), _tiles_mask(n, range(1, nt, 2))
+    group_of = [i % 2 for i in range(nq)]
+    calls = _count_scans(monkeypatch)
+    s, r = _check(sh, rows, q, qd, k, [even, odd], group_of, "below the tile floor")
+    assert len(calls) == 2                              # seed pass + full pass
+    monkeypatch.setattr(HbmIndexShard, "GROUP_LOOP_MIN_TILES", 1)
+    for what, allows, nq_used, scans in (
+            ("disjoint, two blocks against one each", [even, odd], nq, 0),
+            ("disjoint, one block either way", [even, odd], 256, 2),
+            ("overlapping", [even | odd, even], nq, 2)):
+        calls.clear()
+        go = [i % 2 for i in range(nq_used)]
+        mg = sh.make_mask_groups([a.to(DEV) for a in allows], go)
+        s1, r1 = sh.search(q[:nq_used], k, allow=mg)
+        assert len(calls) == scans, what
+        if allows[1] is odd:
+            _same(sh, q[:nq_used], s1, r1, s[:nq_used], r[:nq_used], what)
