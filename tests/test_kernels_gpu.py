@@ -34,6 +34,13 @@ def _close(out, ref, atol, rtol=0.0, what=""):
     assert bad == 0, f"{what}: {bad} elems off, max err {err.max().item():.4g}"
 
 
+def _ids_ok(r, n, what=""):
+    """A search's ids [NQ, k] (k <= n): every one a row of [0, n), no row twice for a query."""
+    assert bool(((r >= 0) & (r < n)).all()), f"{what}: id outside [0, {n})"
+    srt = torch.sort(r.long(), dim=1).values
+    assert not bool((srt[:, 1:] == srt[:, :-1]).any()), f"{what}: a row returned twice for a query"
+
+
 def test_extension_is_native_gfx950():
     from codename_symbiont_amd.ops._ext import hip
 
@@ -594,6 +601,7 @@ def test_index_scan_topk_exact(D, k, n, nq):
     # every returned row's true score equals the returned score
     true = R.row_scores_ref(shard.unit_rows(), q, r)
     _close(s, true, atol=2e-3, what="returned rows")
+    _ids_ok(r, n, "topk ids")
 
 
 def test_index_scan_small_and_partial():
@@ -875,6 +883,8 @@ def test_index_scan_mq_exact(nq, rsplit):
     _close(s1, ref_s, atol=2e-3, what="mq topk scores")
     true = R.row_scores_ref(shard.unit_rows(), q, r1)
     _close(s1, true, atol=2e-3, what="mq returned rows")
+    _ids_ok(r1, n, "mq ids")
+    _ids_ok(r0, n, "list ids")
 
 
 @pytest.mark.parametrize("D", [384, 768, 1024])
@@ -1254,6 +1264,8 @@ def test_index_pruned_search_is_exact(nq, data, tr, monkeypatch):
         assert (r0 == r1).float().mean().item() > 0.999
     true = R.row_scores_ref(shard.unit_rows(), q, r1)
     _close(s1, true, atol=2e-3, what="pruned returned rows")
+    _ids_ok(r1, n, "pruned ids")
+    _ids_ok(r0, n, "exact scan ids")
 
 
 @pytest.mark.parametrize("D", [768, 1024])
@@ -1279,6 +1291,8 @@ def test_index_scan_mq_wide_rows_exact(D):
     assert (r0 == r1).float().mean().item() > 0.999
     true = R.row_scores_ref(shard.unit_rows(), q, r1)
     _close(s1, true, atol=2e-3, what=f"mq{D} returned rows")
+    _ids_ok(r1, n, f"mq{D} ids")
+    _ids_ok(r0, n, f"list{D} ids")
 
 
 @pytest.mark.parametrize("D", [768, 1024])
@@ -2065,6 +2079,7 @@ def test_index_large_k_search_is_exact(k, data):
     _close(R.row_scores_ref(shard.unit_rows(), q, r1), s0, atol=2e-5,
            what=f"top-{k} returned rows")
     assert (r0.int() == r1).float().mean().item() > 0.99
+    _ids_ok(r1, n, f"top-{k} ids")
 
 
 def test_index_scan_mq_overflow_falls_back_exact():
@@ -2129,6 +2144,7 @@ def test_index_scan_fp8_exact_on_decoded_rows(D, k, n, nq):
     assert hits / (nq * min(k, n)) > 0.99
     true = R.row_scores_ref(shard.unit_rows(), qd, r)
     _close(s, true, atol=2e-3, what="fp8 returned rows")
+    _ids_ok(r, n, "fp8 ids")
 
 
 @pytest.mark.gpu
