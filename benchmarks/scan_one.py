@@ -36,6 +36,11 @@ def main() -> None:
                     help="stream forms timed in one process, interleaved: comma list of "
                          "ablation[:centroid] (ablation: stream_config; centroid 0 = the MX-fp4 "
                          "centroid test off), e.g. 0:1,0:0")
+    ap.add_argument("--reserve-sweep", default="",
+                    help="--tier mx4 on the stream image: time the scan's forms in one process, "
+                         "interleaved: comma list of wide:R:depth (wide 0 = the thin form, 1 = "
+                         "the CU-granular one; R = CUs left free, which sizes the block grid; "
+                         "depth 0 = the kernel's default), e.g. 0:0:0,1:0:0,1:64:0,1:64:4")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--thr-add", type=float, default=0.0,
                     help="added to the scan's thresholds (e.g. 10: no row emits -- kernel-only timing)")
@@ -118,6 +123,44 @@ def main() -> None:
         nbytes, kernel = shard.img_i8.shape[1] / STREAM_SUB, "stream-i8"
     else:
         nbytes, kernel = shard.rows_i8.shape[1] + 4, "ldsring-" + ("split" if heavy else "i8")
+    if a.reserve_sweep:
+        if a.tier != "mx4" or shard.img_mx4 is None:
+            raise SystemExit("--reserve-sweep times the MX-fp4 stream scan (--tier mx4)")
+        sweep = [tuple(int(x) for x in f.split(":")) for f in a.reserve_sweep.split(",")]
+        n_cus = shard._n_cus()
+        kw = shard._cent_args(m4)
+
+        def scan_form(wide, R, depth):
+            _, rpb, nrb = shard._i8_geometry(n, a.nq, n_cus, R)
+            P["cnt"].zero_()
+            h.index_scan_stream(shard.img_mx4.data_ptr(), n, shard.img_mx4.shape[0] * STREAM_SUB,
+                                rpb, nrb, m4["q4"].data_ptr(), m4["qs4"].data_ptr(), a.nq,
+                                m4["thr4"].data_ptr(), P["cs"].data_ptr(), P["ci"].data_ptr(),
+                                P["cnt"].data_ptr(), P["cap"], 1, st, dim=a.dim, form=1,
+                                wide=wide, depth=depth, **kw)
+            return rpb, nrb
+
+        times = {f: [] for f in sweep}
+        geo = {}
+        for _ in range(a.rounds):
+            for f in sweep:
+                geo[f] = scan_form(*f)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.iters):
+                    scan_form(*f)
+                torch.cuda.synchronize()
+                times[f].append((time.perf_counter() - t0) * 1e3 / a.iters)
+        for f, ts in times.items():
+            ms = sorted(ts)[len(ts) // 2]
+            print(json.dumps({"bench": "scan_one", "kernel": "stream-mx4", "wide": f[0],
+                              "reserve": f[1], "depth": f[2], "rows": n, "nq": a.nq, "dim": a.dim,
+                              "queries": a.queries, "ms": round(ms, 3),
+                              "ms_all": [round(t, 3) for t in ts],
+                              "TBps": round(n * nbytes / ms / 1e9, 2), "n_rblk": geo[f][1],
+                              "rows_per_blk": geo[f][0],
+                              "cand_mean": round(float(P["cnt"].float().mean()), 1)}), flush=True)
+        return
     forms = [tuple(int(x) for x in f.split(":")) for f in a.ab.split(",")] if a.ab else [None]
     cent = [True]   # the MX-fp4 centroid test (a 5th form field: 0 = off)
     times = {f: [] for f in forms}

@@ -569,6 +569,12 @@ class HbmIndexShard:
         # >= 512 seeded queries on a 384-wide bf16 shard (the per-rank shape of the sharded search
         # at N >= 2 GPUs): the 512-query-per-workgroup candidate-emitting kernel (index_mq.hip)
         self.scan_cus = 0      # 0 = every CU (see _n_cus)
+        # CUs the fp4 stream scan of a split-phase search (search_begin / search_end) leaves
+        # whole for the work its caller runs beside it; 0 = none, the thin form (_scan_reserve;
+        # SYMB_SCAN_RESERVE for A/B runs).  scan_depth: the fp4 scan's sub-tiles in flight per
+        # wave at dim 384 (0 = the kernel's 3; 4, 5; SYMB_SCAN_DEPTH)
+        self.scan_reserve = int(os.environ.get("SYMB_SCAN_RESERVE", "") or self.SCAN_RESERVE)
+        self.scan_depth = int(os.environ.get("SYMB_SCAN_DEPTH", "") or 0)
         self.scan_mq = True
         self.mq_min_nq = 256   # smallest batch for the emitting kernel (< 512: a 256-query form)
         # smallest batch for the int8-pruned search: its scan costs about the same for 1..256
@@ -1519,7 +1525,7 @@ class HbmIndexShard:
             return {"full": self.search(q_unit, k, n_cus)}
         if (self.device.type == "cuda" and self.prune and not self.prefilter and 0 < k <= 16
                 and q.shape[0] >= self.prune_min_nq and self._seed_rows(self.visible, k)):
-            ctx = self._pruned_begin(q, k, n_cus)
+            ctx = self._pruned_begin(q, k, n_cus, split=True)
             if ctx is not None:
                 if tomb:   # search_end checks the result against the live mask of THIS begin
                     ctx["live"] = self._live()
@@ -2334,10 +2340,11 @@ class HbmIndexShard:
         ctx = self._pruned_begin(q_unit, k, n_cus)
         return None if ctx is None else self._pruned_end(ctx)
 
-    def _pruned_begin(self, q_unit, k: int, n_cus):
+    def _pruned_begin(self, q_unit, k: int, n_cus, split: bool = False):
         """Query-side half of the pruned search: int8 queries, the exact sample, T, thresholds and
         the route flag -- everything before the full-shard scan, on the current stream, for the
-        rows visible NOW (a pipelined caller runs it for batch i + 1 under batch i's scan)."""
+        rows visible NOW (a pipelined caller runs it for batch i + 1 under batch i's scan).
+        ``split``: the caller is ``search_begin`` and left ``n_cus`` to the shard (_scan_reserve)."""
         from ..ops._ext import hip, stream_handle
 
         n, NQ, kmax = self.visible, q_unit.shape[0], 16
@@ -2353,14 +2360,16 @@ class HbmIndexShard:
             plan, ts = self._tile_sample_plan(n, ts, want_idx=False), ts - 1
         if plan is None:
             return None
+        split = split and n_cus is None
         if n_cus is None:
             n_cus = self._n_cus()
+        reserve = self._scan_reserve(split, n_cus, NQ)
         h, dev, cap = hip(), self.device, self.PRUNE_CAP
         st = stream_handle(dev)
         ts, nv, t0, _ = plan
         tcap = n - t0
         dense_tail = NQ <= self.tail_dense_max_nq
-        geo = self._i8_geometry(n, NQ, n_cus)
+        geo = self._i8_geometry(n, NQ, n_cus, reserve)
         n_rblk = geo[2]
         # one int32 workspace for every counter and flag of the search, cleared by the query
         # quantiser on its way (no memset launches): the sample's and the final scan's candidate
@@ -2445,7 +2454,8 @@ class HbmIndexShard:
                       tail_cnt=0 if tcnt is None else tcnt.data_ptr(), tail_cap=tcap, tail_off=t0,
                       tail_ld=tail_ld, zeroed=True)
         ctx = dict(q=q_unit, k=k, n=n, n_cus=n_cus, q8=q8, sq=sq, thr=thr, T=T, dense=dense,
-                   blk=blk, geo=geo, heavy=heavy, gen=self._calib_gen, mx4=None, ws=ws)
+                   blk=blk, geo=geo, heavy=heavy, gen=self._calib_gen, mx4=None, ws=ws,
+                   wide=reserve > 0, hint_mx4=bool(self._tier_mx4 and self.mx4_on))
         # 3. the MX-fp4 first tier (mx4_select): when every query's k-th score sits so far above
         #    the corpus bulk that even the coarse fp4 bound (|q| E4 + |q - q~| X4, ~0.25 on unit
         #    rows) leaves few rows in its band -- self / near-duplicate queries, such as the
@@ -2493,9 +2503,28 @@ class HbmIndexShard:
         return dict(cent4=m4["c4"].data_ptr(), centqs=m4["cqs"].data_ptr(),
                     centR=m4["cR"].data_ptr(), bounds4=self.mx4_bounds.data_ptr())
 
-    def _i8_geometry(self, n: int, NQ: int, n_cus: int):
+    # default of ``scan_reserve`` (profiles/r7_reserve/README.md has the sweep)
+    SCAN_RESERVE = 96
+
+    def _scan_reserve(self, split: bool, n_cus: int, NQ: int) -> int:
+        """CUs the stream scans of this search leave whole (``scan_reserve``), 0 outside the one
+        case it is for: a split-phase search (``search_begin`` with ``n_cus=None``: its caller
+        splits to run work beside the scan) while the tier hint says MX-fp4, on a shard whose
+        two tiers are the stream scans.  That scan is HBM-bound and keeps its bandwidth on fewer
+        CUs; the int8 scan is MFMA-bound and would lose its CUs' share, so a search the hint
+        gives to int8 -- like a plain ``search`` -- keeps every CU.  A wrong hint costs only
+        speed: the other tier runs on the same, smaller block grid."""
+        if not (split and self.scan_reserve > 0 and self._tier_mx4 and self.mx4_on and self.stream
+                and self.img_mx4 is not None and self.img_i8 is not None
+                and not self._i8_heavy and not self.i8_ring
+                and self.prune_route and NQ <= self.tail_dense_max_nq):   # (the tier is enqueued)
+            return 0
+        return max(0, min(int(self.scan_reserve), n_cus - 1))
+
+    def _i8_geometry(self, n: int, NQ: int, n_cus: int, reserve: int = 0):
         """(rsplit, rows_per_blk, n_rblk) of the int8 scan over n rows: ~one workgroup per CU
-        slot, whole tiles per block."""
+        slot, whole tiles per block.  ``reserve`` (_scan_reserve; the stream scans only): CUs the
+        CU-granular scan leaves whole."""
         from ..ops._ext import hip
 
         h = hip()
@@ -2523,7 +2552,13 @@ class HbmIndexShard:
             # (>= 8192 rows per block: the route estimates each block from the exact sample's
             # 1-in-2^5 tiles, so a block needs a few sampled tiles -- ~1k-row blocks saw 0 or 1
             # and left crowded blocks to the int8 scan)
-            n_rblk = max(1, min(math.ceil(n / 8192), 1024, max(1, round(n_cus * wpc / n_qblk))))
+            # With a reserve R the scans run in the CU-granular form (index_stream.hip, PACK):
+            # 4 waves per workgroup and one workgroup per CU, so wpc n_rblk n_qblk / 4 workgroups
+            # occupy n_cus - R CUs: n_rblk ~ 4 (n_cus - R) / n_qblk for the fp4 form.  The same
+            # limits hold: >= 8192 rows per block, <= 1024 blocks (ROUTE_MAX_BLOCKS),
+            # rows_per_blk a multiple of 128.
+            slots = (n_cus - reserve) * wpc if reserve > 0 else n_cus * wpc
+            n_rblk = max(1, min(math.ceil(n / 8192), 1024, max(1, round(slots / n_qblk))))
             rows_per_blk = _round_up(max(1, math.ceil(n / n_rblk)), 128)
             n_rblk = max(1, math.ceil(n / rows_per_blk))
             return rsplit, rows_per_blk, n_rblk
@@ -2596,39 +2631,61 @@ class HbmIndexShard:
                     m4[t].record_stream(cur)
         tier = None if m4 is None else m4["nv"]
         gate, want = (0, 0) if tier is None else (tier.data_ptr(), 1)
-        if self.img_i8 is not None and not ctx["heavy"]:   # the stream scan (index_stream.hip)
-            h.index_scan_stream(self.img_i8.data_ptr(), n_scan, self.img_i8.shape[0] * STREAM_SUB,
-                                rows_per_blk, n_rblk, q8.data_ptr(), 0, NQ, thr.data_ptr(),
-                                cs.data_ptr(), ci.data_ptr(), cnt.data_ptr(), cap, self.scan_xcd,
-                                st, skip=skip, dim=self.dim, form=0, gate=gate, gate_want=want,
-                                zero_cnt=0)
-        else:
-            h.index_scan_i8(self.rows_i8.data_ptr(), self.sx_i8.data_ptr(), n_scan,
-                            self.rows_i8.shape[0], rows_per_blk, n_rblk,
-                            q8.data_ptr(), NQ, thr.data_ptr(), cs.data_ptr(), ci.data_ptr(),
-                            cnt.data_ptr(), cap, self.scan_xcd, st, rsplit, skip=skip,
-                            dim=self.dim, heavy=ctx["heavy"], sq=ctx["sq"].data_ptr(), gate=gate,
-                            gate_want=want, zero_cnt=0)
-        if m4 is not None and self.img_mx4 is not None:
-            # (runs: the device counter of searches whose first tier was this scan)
-            runs = 0
-            if self.mq_stats or self.tier_stats:
-                if self._mx4_tot is None:
-                    self._mx4_tot = torch.zeros(1, dtype=torch.int32, device=dev)
-                runs = self._mx4_tot.data_ptr()
-            h.index_scan_stream(self.img_mx4.data_ptr(), n_scan, self.img_mx4.shape[0] * STREAM_SUB,
-                                rows_per_blk, n_rblk, m4["q4"].data_ptr(), m4["qs4"].data_ptr(),
+        wide = int(ctx["wide"])   # the CU-granular stream scans on the reserve's block grid
+
+        def tier_i8():
+            if self.img_i8 is not None and not ctx["heavy"]:   # the stream scan (index_stream.hip)
+                h.index_scan_stream(self.img_i8.data_ptr(), n_scan,
+                                    self.img_i8.shape[0] * STREAM_SUB, rows_per_blk, n_rblk,
+                                    q8.data_ptr(), 0, NQ, thr.data_ptr(), cs.data_ptr(),
+                                    ci.data_ptr(), cnt.data_ptr(), cap, self.scan_xcd, st,
+                                    skip=skip, dim=self.dim, form=0, gate=gate, gate_want=want,
+                                    zero_cnt=0, wide=wide)
+            else:
+                h.index_scan_i8(self.rows_i8.data_ptr(), self.sx_i8.data_ptr(), n_scan,
+                                self.rows_i8.shape[0], rows_per_blk, n_rblk,
+                                q8.data_ptr(), NQ, thr.data_ptr(), cs.data_ptr(), ci.data_ptr(),
+                                cnt.data_ptr(), cap, self.scan_xcd, st, rsplit, skip=skip,
+                                dim=self.dim, heavy=ctx["heavy"], sq=ctx["sq"].data_ptr(),
+                                gate=gate, gate_want=want, zero_cnt=0)
+
+        def tier_mx4():
+            if self.img_mx4 is not None:
+                # (runs: the device counter of searches whose first tier was this scan)
+                runs = 0
+                if self.mq_stats or self.tier_stats:
+                    if self._mx4_tot is None:
+                        self._mx4_tot = torch.zeros(1, dtype=torch.int32, device=dev)
+                    runs = self._mx4_tot.data_ptr()
+                h.index_scan_stream(self.img_mx4.data_ptr(), n_scan,
+                                    self.img_mx4.shape[0] * STREAM_SUB, rows_per_blk, n_rblk,
+                                    m4["q4"].data_ptr(), m4["qs4"].data_ptr(), NQ,
+                                    m4["thr4"].data_ptr(), cs.data_ptr(), ci.data_ptr(),
+                                    cnt.data_ptr(), cap, self.scan_xcd, st, skip=skip,
+                                    dim=self.dim, form=1, gate=m4["nv"].data_ptr(), gate_want=0,
+                                    zero_cnt=0, runs=runs, wide=wide,
+                                    depth=self.scan_depth if self.dim == 384 else 0,
+                                    **self._cent_args(m4))
+            else:
+                h.index_scan_i8(self.rows_mx4.data_ptr(), self.sc_mx4.data_ptr(), n_scan,
+                                self.rows_mx4.shape[0], rows_per_blk, n_rblk, m4["q4"].data_ptr(),
                                 NQ, m4["thr4"].data_ptr(), cs.data_ptr(), ci.data_ptr(),
-                                cnt.data_ptr(), cap, self.scan_xcd, st, skip=skip, dim=self.dim,
-                                form=1, gate=m4["nv"].data_ptr(), gate_want=0, zero_cnt=0,
-                                runs=runs, **self._cent_args(m4))
-        elif m4 is not None:
-            h.index_scan_i8(self.rows_mx4.data_ptr(), self.sc_mx4.data_ptr(), n_scan,
-                            self.rows_mx4.shape[0], rows_per_blk, n_rblk, m4["q4"].data_ptr(), NQ,
-                            m4["thr4"].data_ptr(), cs.data_ptr(), ci.data_ptr(), cnt.data_ptr(),
-                            cap, self.scan_xcd, st, rsplit, skip=skip, dim=self.dim,
-                            sq=m4["qs4"].data_ptr(), form=1, gate=m4["nv"].data_ptr(),
-                            gate_want=0)
+                                cnt.data_ptr(), cap, self.scan_xcd, st, rsplit, skip=skip,
+                                dim=self.dim, sq=m4["qs4"].data_ptr(), form=1,
+                                gate=m4["nv"].data_ptr(), gate_want=0)
+
+        # The tier the hint expects goes first: the other launch exits at its gate, but even a
+        # no-op launch of these kernels waits for SIMDs (the CU-granular form: a CU) with a free
+        # register file, and in front of the real scan that wait is on the step's critical path.
+        # Both write the same buffers and exactly one runs, so the order changes no result.
+        if m4 is None:
+            tier_i8()
+        elif ctx["hint_mx4"]:
+            tier_mx4()
+            tier_i8()
+        else:
+            tier_i8()
+            tier_mx4()
         # 3'. the bf16 emitting scan of the blocks the route listed, at the exact threshold T,
         #     into the same candidate buffers (no launch work when none is listed)
         if self.prune_route:

@@ -148,7 +148,8 @@ int symb_index_scan_stream(const void* img, int n_valid, int alloc_rows, int row
                            float* cand_s, int* cand_i, int* cand_n, int cap, int xcd,
                            hipStream_t st, const int* skip, int dim, int form, const int* gate,
                            int gate_want, int zero_cnt, int* runs, const void* cent4,
-                           const void* centqs, const float* centR, const float* bounds4);
+                           const void* centqs, const float* centR, const float* bounds4, int wide,
+                           int depth);
 int symb_mx4_centroids(const void* Xq, const void* QS, int NQ, int dim, void* C4, void* CS,
                        float* R, hipStream_t st);
 int symb_append_rows(const void* src, int n, int dim, void* rows, int r0, void* img8, float* b8,
@@ -675,20 +676,22 @@ PYBIND11_MODULE(_hip, m) {
                                 uptr Q, uptr qsc, int NQ, uptr thr, uptr cand_s, uptr cand_i,
                                 uptr cand_n, int cap, int xcd, uptr st, uptr skip, int dim,
                                 int form, uptr gate, int gate_want, int zero_cnt, uptr runs,
-                                uptr cent4, uptr centqs, uptr centR, uptr bounds4) {
+                                uptr cent4, uptr centqs, uptr centR, uptr bounds4, int wide,
+                                int depth) {
     check(symb_index_scan_stream(P<void>(img), n_valid, alloc_rows, rows_per_blk, n_rblk,
                                  P<void>(Q), P<void>(qsc), NQ, P<const float>(thr),
                                  P<float>(cand_s), P<int>(cand_i), P<int>(cand_n), cap, xcd, S(st),
                                  P<const int>(skip), dim, form, P<const int>(gate), gate_want,
                                  zero_cnt, P<int>(runs), P<void>(cent4), P<void>(centqs),
-                                 P<const float>(centR), P<const float>(bounds4)),
+                                 P<const float>(centR), P<const float>(bounds4), wide, depth),
           "index_scan_stream");
   }, py::arg("img"), py::arg("n_valid"), py::arg("alloc_rows"), py::arg("rows_per_blk"),
      py::arg("n_rblk"), py::arg("Q"), py::arg("qsc"), py::arg("NQ"), py::arg("thr"),
      py::arg("cand_s"), py::arg("cand_i"), py::arg("cand_n"), py::arg("cap"), py::arg("xcd"),
      py::arg("stream"), py::arg("skip") = 0, py::arg("dim") = 384, py::arg("form") = 0,
      py::arg("gate") = 0, py::arg("gate_want") = 0, py::arg("zero_cnt") = 1, py::arg("runs") = 0,
-     py::arg("cent4") = 0, py::arg("centqs") = 0, py::arg("centR") = 0, py::arg("bounds4") = 0);
+     py::arg("cent4") = 0, py::arg("centqs") = 0, py::arg("centR") = 0, py::arg("bounds4") = 0,
+     py::arg("wide") = 0, py::arg("depth") = 0);
   m.def("mx4_centroids", [](uptr Xq, uptr QS, int NQ, int dim, uptr C4, uptr CS, uptr R, uptr st) {
     check(symb_mx4_centroids(P<void>(Xq), P<void>(QS), NQ, dim, P<void>(C4), P<void>(CS),
                              P<float>(R), S(st)),

@@ -101,10 +101,20 @@ __device__ __forceinline__ float max16(const float (&v)[16]) {
 // Workgroup lb = (row block rb, query block qb); cand_n must be zeroed by the caller.
 // ABL (timing ablations, wrong results): 1 = no emission test (the accumulators kept live),
 // 2 = no sub-tile loads after the prologue (the first DEPTH sub-tiles re-used).
-template <int FMT, int D, int ABL = 0>
-__global__ __launch_bounds__((64 * SGeo<FMT, D>::NW), 1) void scan_stream_kernel(
+//
+// PACK: thin workgroups per launched workgroup.  PACK = 1 is the thin form: NW waves, which the
+// dispatcher spreads over every CU's SIMDs.  PACK = 4 / NW is the CU-granular form: four waves,
+// one per SIMD, that together hold a CU's register file (occupancy 1 each), so at most one
+// workgroup fits a CU and a grid of G workgroups occupies exactly G CUs and leaves the others
+// whole for kernels on other streams.  Group p = wave / NW of workgroup b works exactly as thin
+// workgroup PACK b + p does (xcd_remap applied to b): no barrier, no shared state, its own LDS
+// stage.  A group whose block lies past the n_lb = n_rblk * n_qblk blocks returns.
+// DEPTH_: sub-tiles in flight per wave (0: SGeo's).
+template <int FMT, int D, int ABL = 0, int PACK = 1, int DEPTH_ = 0>
+__global__ __launch_bounds__((64 * SGeo<FMT, D>::NW * PACK), 1) void scan_stream_kernel(
     const uint8_t* __restrict__ img, int n_valid, int rows_per_blk, const uint8_t* __restrict__ Q,
-    const uint32_t* __restrict__ qsc, int NQ, int n_qblk, int xcd, const float* __restrict__ thr_in,
+    const uint32_t* __restrict__ qsc, int NQ, int n_qblk, int n_lb, int xcd,
+    const float* __restrict__ thr_in,
     float* __restrict__ cand_s, int* __restrict__ cand_i, int* __restrict__ cand_n, int cap,
     const int* __restrict__ skip, const int* __restrict__ gate, int gate_want,
     int* __restrict__ runs, const uint8_t* __restrict__ cent4, const uint32_t* __restrict__ centqs,
@@ -112,14 +122,22 @@ __global__ __launch_bounds__((64 * SGeo<FMT, D>::NW), 1) void scan_stream_kernel
   using S = SDim<FMT, D>;
   using G = SGeo<FMT, D>;
   constexpr int NKS = S::NKS, NSC = S::NSC ? S::NSC : 1, REC = S::REC;
-  constexpr int SETS = G::SETS, DEPTH = G::DEPTH, STW = G::STW;
+  constexpr int SETS = G::SETS, DEPTH = DEPTH_ ? DEPTH_ : G::DEPTH, STW = G::STW;
+  static_assert(PACK >= 1 && G::NW * PACK <= 4, "one wave per SIMD");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
-  const int lb = xcd ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+  const int lane = threadIdx.x & 63, wave_wg = threadIdx.x >> 6, h = lane >> 5;
+  // (the thin form keeps its own plain expressions: the int8 scan is MFMA-bound and its
+  // schedule moved with the general ones -- 100M x 384: 9.85 -> 10.41 ms, profiles/r7_reserve/)
+  const int wave = PACK == 1 ? wave_wg : wave_wg % G::NW;   // (within the thin workgroup)
+  const int wg = xcd ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+  const int lb = PACK == 1 ? wg : PACK * wg + wave_wg / G::NW;
   const int qb = lb % n_qblk, rb = lb / n_qblk;
   if (gate != nullptr && *gate != gate_want) return;   // (no barrier in this kernel)
   // runs (optional): counts the launches that passed the gate (the MX-fp4 tier's batches)
   if (runs != nullptr && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(runs, 1);
+  if constexpr (PACK > 1) {
+    if (lb >= n_lb) return;                       // (the last workgroup's spare groups)
+  }
   if (skip != nullptr && skip[rb] != 0) return;   // (routed to the bf16 scan)
   const int row_begin = rb * rows_per_blk;
   const int row_end = min(row_begin + rows_per_blk, n_valid);
@@ -181,7 +199,7 @@ __global__ __launch_bounds__((64 * SGeo<FMT, D>::NW), 1) void scan_stream_kernel
   }
 
   // ---- per-wave candidate stage (LDS) ----
-  char* stage = smem + wave * G::STAGE;
+  char* stage = smem + wave_wg * G::STAGE;
   float* st_s = reinterpret_cast<float*>(stage);
   int* st_r = reinterpret_cast<int*>(stage + STW * 4);
   uint16_t* st_q = reinterpret_cast<uint16_t*>(stage + STW * 8);
@@ -810,20 +828,23 @@ struct CentArgs {   // the MX-fp4 centroid test's inputs (all nullptr: off)
   const float* b4;
 };
 
-template <int F, int D, int ABL = 0>
+// WIDE: the CU-granular form (PACK = 4 / NW thin workgroups per workgroup; a 4-wave thin form is
+// its own CU-granular form); DEPTH_: sub-tiles in flight (0: SGeo's)
+template <int F, int D, int ABL = 0, bool WIDE = false, int DEPTH_ = 0>
 static int launch_stream(const void* img, int n_valid, int rows_per_blk, int n_rblk, const void* Q,
                          const void* qsc, int NQ, const float* thr, float* cand_s, int* cand_i,
                          int* cand_n, int cap, int xcd, hipStream_t st, const int* skip,
                          const int* gate, int gate_want, int* runs, CentArgs ca) {
   using G = SGeo<F, D>;
-  const int n_qblk = (NQ + G::QPB - 1) / G::QPB;
-  constexpr int lds = G::STAGE * G::NW;
-  if (lds > 64 * 1024) set_max_lds<scan_stream_kernel<F, D, ABL>>(lds);
-  hipLaunchKernelGGL((scan_stream_kernel<F, D, ABL>), dim3(n_rblk * n_qblk), dim3(64 * G::NW), lds,
-                     st, (const uint8_t*)img, n_valid, rows_per_blk, (const uint8_t*)Q,
-                     (const uint32_t*)qsc, NQ, n_qblk, xcd, thr, cand_s, cand_i, cand_n, cap, skip,
-                     gate, gate_want, runs, (const uint8_t*)ca.c4, (const uint32_t*)ca.cqs, ca.R,
-                     ca.b4);
+  constexpr int PACK = WIDE ? 4 / G::NW : 1;
+  const int n_qblk = (NQ + G::QPB - 1) / G::QPB, n_lb = n_rblk * n_qblk;
+  constexpr int lds = G::STAGE * G::NW * PACK;
+  if (lds > 64 * 1024) set_max_lds<scan_stream_kernel<F, D, ABL, PACK, DEPTH_>>(lds);
+  hipLaunchKernelGGL((scan_stream_kernel<F, D, ABL, PACK, DEPTH_>), dim3((n_lb + PACK - 1) / PACK),
+                     dim3(64 * G::NW * PACK), lds, st, (const uint8_t*)img, n_valid, rows_per_blk,
+                     (const uint8_t*)Q, (const uint32_t*)qsc, NQ, n_qblk, n_lb, xcd, thr, cand_s,
+                     cand_i, cand_n, cap, skip, gate, gate_want, runs, (const uint8_t*)ca.c4,
+                     (const uint32_t*)ca.cqs, ca.R, ca.b4);
   return (int)hipGetLastError();
 }
 
@@ -832,14 +853,22 @@ static int launch_stream(const void* img, int n_valid, int rows_per_blk, int n_r
 // form 0: int8 (Q = [NQ][dim] int8, qsc unused); 1: MX-fp4 (Q = [NQ][dim / 2] nibbles, qsc =
 // [NQ][2 NSC] scale dwords).  cand_n is zeroed here iff zero_cnt (else the caller's zeroed
 // workspace); gate != nullptr: the launch runs only if *gate == gate_want; runs (optional) is
-// incremented once by a launch that ran.
+// incremented once by a launch that ran.  wide: the CU-granular form (scan_stream_kernel PACK:
+// ceil(n_rblk n_qblk / PACK) workgroups, each a whole CU) instead of the thin one.  depth: sub-tiles
+// in flight per wave, 0 = the form's default; 4 and 5 exist for MX-fp4 at dim 384.
 int symb_index_scan_stream(const void* img, int n_valid, int alloc_rows, int rows_per_blk,
                            int n_rblk, const void* Q, const void* qsc, int NQ, const float* thr,
                            float* cand_s, int* cand_i, int* cand_n, int cap, int xcd,
                            hipStream_t st, const int* skip, int dim, int form, const int* gate,
                            int gate_want, int zero_cnt, int* runs, const void* cent4,
-                           const void* centqs, const float* centR, const float* bounds4) {
+                           const void* centqs, const float* centR, const float* bounds4, int wide,
+                           int depth) {
   if (NQ <= 0) return 0;
+  if (wide < 0 || wide > 1) return -1;
+  if (depth == SGeo<SF_MX4, 384>::DEPTH && form == 1 && dim == 384) depth = 0;
+  if (depth != 0 && !(form == 1 && dim == 384 && (depth == 4 || depth == 5))) return -1;
+  // (the ablations exist in the thin form at the default depth)
+  if ((depth != 0 || wide) && g_stream_abl != 0) return -1;
   if (cent4 != nullptr && (form != 1 || centqs == nullptr || centR == nullptr || bounds4 == nullptr))
     return -1;
   const CentArgs ca{cent4, centqs, centR, bounds4};
@@ -852,14 +881,21 @@ int symb_index_scan_stream(const void* img, int n_valid, int alloc_rows, int row
     hipError_t e = hipMemsetAsync(cand_n, 0, sizeof(int) * (size_t)NQ, st);
     if (e != hipSuccess) return (int)e;
   }
-#define L(F, D_, A_) launch_stream<F, D_, A_>(img, n_valid, rows_per_blk, n_rblk, Q, qsc, NQ, thr, \
-                                              cand_s, cand_i, cand_n, cap, xcd, st, skip, gate,   \
-                                              gate_want, runs, ca)
-#define LD(F, D_) (g_stream_abl == 1 ? L(F, D_, 1) : g_stream_abl == 2 ? L(F, D_, 2) : L(F, D_, 0))
+#define L(F, D_, A_, W_, P_)                                                                      \
+  launch_stream<F, D_, A_, W_, P_>(img, n_valid, rows_per_blk, n_rblk, Q, qsc, NQ, thr, cand_s,   \
+                                   cand_i, cand_n, cap, xcd, st, skip, gate, gate_want, runs, ca)
+#define LW(F, D_, A_) (wide ? L(F, D_, A_, true, 0) : L(F, D_, A_, false, 0))
+#define LD(F, D_)                                 \
+  (g_stream_abl == 1   ? L(F, D_, 1, false, 0)    \
+   : g_stream_abl == 2 ? L(F, D_, 2, false, 0)    \
+                       : LW(F, D_, 0))
+  if (depth == 4) return wide ? L(SF_MX4, 384, 0, true, 4) : L(SF_MX4, 384, 0, false, 4);
+  if (depth == 5) return wide ? L(SF_MX4, 384, 0, true, 5) : L(SF_MX4, 384, 0, false, 5);
   if (dim == 384) return form ? LD(SF_MX4, 384) : LD(SF_I8, 384);
   if (dim == 768) return form ? LD(SF_MX4, 768) : LD(SF_I8, 768);
   return form ? LD(SF_MX4, 1024) : LD(SF_I8, 1024);
 #undef LD
+#undef LW
 #undef L
 }
 
