@@ -9,6 +9,8 @@ import pytest
 import torch
 
 from codename_symbiont_amd.ops import reference as R
+# the MX fp8 quantiser rule and its decoder: one copy, shared with the fp8 hand-off probe
+from fp8_probe import mx_decode as _mx_decode, mx_quant as _mx_quant_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -2260,24 +2262,6 @@ def test_gemm_fp8(M, N, K, epi):
     del ref
 
 
-def _mx_quant_ref(x, block=32):
-    """Host MX fp8 quantiser: E8M0 exponent e per 32 consecutive columns (smallest e with
-    amax * 2^-e < 448), e4m3 bytes of x * 2^-e.  Returns (bytes uint8 [M,K], exps int [M,K/32])."""
-    M, K = x.shape
-    xb = x.float().view(M, K // block, block)
-    amax = xb.abs().amax(-1)
-    _, ex = torch.frexp(amax / 448.0)
-    ex = torch.where(amax > 0, ex.clamp(-127, 127), torch.full_like(ex, -127))
-    q = (xb * torch.pow(2.0, -ex.float())[..., None]).to(torch.float8_e4m3fn)
-    return q.view(M, K).view(torch.uint8), ex
-
-
-def _mx_decode(q8, ex, block=32):
-    M, K = q8.shape
-    v = q8.view(torch.float8_e4m3fn).float().view(M, K // block, block)
-    return (v * torch.pow(2.0, ex.float())[..., None]).view(M, K)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("waves", [4, 8, 16, 256])
 @pytest.mark.parametrize("M,N,K", [(300, 1536, 384), (1000, 4096, 1024), (77, 3072, 768),
@@ -2421,7 +2405,8 @@ def test_encoder_fp8_close_to_fp32_oracle(model):
     above the smallest planted effect itself (P = 0.19 / 0.23): no threshold separates a correct
     fp8 encoder from a miswired one there (test_encoder_probe_cpu.py pins that measurement).  The
     fp8 layers take their pointers from the same positional ``keys`` list as the bf16 layers, which
-    the wiring test covers; their own hand-offs (fp8_layer) stay checked by this cosine only."""
+    the wiring test covers; their own hand-offs (fp8_layer) are checked step by step, each against
+    a recomputation from its observed inputs, in test_encoder_fp8_gpu.py (tests/fp8_probe.py)."""
     from codename_symbiont_amd.models import get_config
     from codename_symbiont_amd.models.encoder import HipEncoder, TorchEncoder, synthetic_batch
     from codename_symbiont_amd.models.weights import load_params
