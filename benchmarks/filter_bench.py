@@ -34,24 +34,28 @@ Masks: all ones; uniform random bits; "documents" = runs of 200 consecutive rows
 (packed bits + live-tile list) and the gather's row list are built once per mask, outside the
 timed loops; ``mask_ms`` is that one-off cost of the RowMask.
 
---groups 2,4,8 (bf16 or --dtype fp8, k <= 32; replaces the per-mask run): a mask per query.  For every case of
---group-cases and every G, G masks are built and the nq queries dealt over them in turn
+--groups 2,4,8 (bf16 at k <= 32, --dtype fp8 at k <= 128; replaces the per-mask run): a mask per
+query.  For every case of --group-cases and every G, G masks are built and the nq queries dealt over them in turn
 (query i under mask i % G); per case and G, alternated in one process:
 
   grouped       shard.search(q, k, allow=MaskGroups): the grouped scan (index_filter_group.hip;
-                index_filter_group_fp8.hip on an fp8 shard), or per chunk whatever
+                index_filter_group_fp8.hip on an fp8 shard; at k > 32 on an fp8 shard the
+                grouped emitting scan, index_emit_group_fp8.hip, "emit"), or per chunk whatever
                 ``grouped_routes`` names (--force-scan: always the scan)
   group_loop    the same call with the grouped scan off: one single-mask search per group, the
                 only way to answer such a burst before the grouped scan
-  union_floor   all nq queries under the union of the masks in the single-mask scan: the rows
-                the grouped scan has to walk, without its per-lane mask select
+  union_floor   all nq queries under the union of the masks in the single-mask scan (at
+                k > 32 the single-mask emitting search): the rows the grouped scan has to walk,
+                without its per-lane mask select
   single_mask   all nq queries under mask 0 alone (a search that never enters the new kernel)
 
 Cases: n1 = must_not-style, each mask excludes a different 1 % of the rows (as documents);
 d1 / d0.1 = disjoint document masks of 1 % / 0.1 % each; u50 = uniform 50 %, a seed per mask.
 Every line carries grouped_equals_loop (scores bit for bit, rows outside runs of equal scores;
 on fp8 a last slot that differs without an equal neighbour must be proved a tie as above, and
-last_slot_ties_proved counts them).
+last_slot_ties_proved counts them).  At k > 32 every line also carries, from the grouped
+variant's last chunk, ``overflow`` (1: the chunk's candidates passed LARGE_K_CAP and the per-mask
+loop answered it), ``max_candidates`` (the most one query emitted) and ``cap``.
 
     python benchmarks/filter_bench.py [--rows 100000000] [--dim 384] [--nq 256] [--k 10]
         [--masks ones,u50,u10,u1,d10,d1,d0.1] [--rounds 3] [--iters 5] [--out FILE]
@@ -179,6 +183,15 @@ def run_groups(a, shard, q, emit, base) -> None:
             for v, fn in variants.items():       # results first (also the warm-up)
                 res[v] = fn()
                 torch.cuda.synchronize()
+            large_k_info = {}
+            if k > 32:       # the grouped emitting route's record (each search overwrites it)
+                shard._filter_large_k_last = None
+                grouped(2)
+                torch.cuda.synchronize()
+                last = shard._filter_large_k_last
+                if last is not None:
+                    large_k_info = {"overflow": int(last[1]), "max_candidates": int(last[0].max()),
+                                    "cap": int(shard.LARGE_K_CAP)}
             (gs, gr), (ls, lr) = res["grouped"], res["group_loop"]
             tie = torch.zeros_like(gs, dtype=torch.bool)
             tie[:, 1:] |= gs[:, 1:] == gs[:, :-1]
@@ -188,13 +201,13 @@ def run_groups(a, shard, q, emit, base) -> None:
             if shard.dtype == "fp8" and torch.equal(gs, ls) and not same:
                 same, proved = rows_equal_outside_ties(shard, q, gs, gr, lr)
             del res
-            routes = ["loop" if shard._loop_keeps_chunk(mg.chunk(c), k) else "scan"
-                      for c in range(mg.n_chunks)]
+            routes = ["loop" if shard._loop_keeps_chunk(mg.chunk(c), k) else
+                      "emit" if k > 32 else "scan" for c in range(mg.n_chunks)]
             info = dict(base, case=case, groups=G, len_groups=len(mg), chunks=mg.n_chunks,
                         grouped_routes=routes,
                         union_live_tiles=int(umask.n_live),
                         live_tiles=[int(m.n_live) for m in masks],
-                        groups_ms=round(groups_ms, 3), grouped_equals_loop=same)
+                        groups_ms=round(groups_ms, 3), grouped_equals_loop=same, **large_k_info)
             if proved is not None:
                 info["last_slot_ties_proved"] = proved
             times = {v: [] for v in variants}
@@ -260,8 +273,13 @@ def main() -> None:
     if fp8:
         base["dtype"] = "fp8"
     if a.groups:
-        if k > 32:
-            raise SystemExit("--groups measures the grouped list scans: k <= 32")
+        if k > 32 and not (fp8 and k <= shard.K_MAX_HIP):
+            raise SystemExit("--groups at k > 32 measures the grouped emitting scan of an fp8 "
+                             f"shard: --dtype fp8, k <= {shard.K_MAX_HIP}")
+        if k > 32 and not shard._group_large_k_serves(k, [None, None]):
+            raise SystemExit("--groups at k > 32: this shard is below FP8_LARGE_K_MIN_ROWS rows "
+                             "or of a width the emitting scan is not built for (the per-mask "
+                             "loop would answer both variants)")
         if a.force_scan:
             shard.GROUP_LOOP_MIN_TILES = 1 << 62
         run_groups(a, shard, q, emit, dict(base, bench="filter_bench_groups"))

@@ -1714,6 +1714,16 @@ class HbmIndexShard:
         return ((self.dtype == "bf16" and self.dim in FILTER_DIMS)
                 or (self.dtype == "fp8" and self.dim in FILTER_FP8_DIMS))
 
+    def _group_large_k_serves(self, k: int, groups: MaskGroups) -> bool:
+        """The grouped emitting e4m3 scan (index_emit_group_fp8.hip) serves this search: an fp8
+        shard on a GPU at a width in FILTER_LARGE_K_FP8_DIMS, 32 < k <= K_MAX_HIP, with
+        FP8_LARGE_K_MIN_ROWS visible rows or more (the single-mask route's own gate: below it
+        the per-mask loop's matmul keeps the search) and GROUP_SCAN_MIN_GROUPS masks or more."""
+        return (self.device.type == "cuda" and self.dtype == "fp8"
+                and self.dim in FILTER_LARGE_K_FP8_DIMS and 32 < k <= self.K_MAX_HIP
+                and self.visible >= self.FP8_LARGE_K_MIN_ROWS
+                and len(groups) >= self.GROUP_SCAN_MIN_GROUPS)
+
     def _search_grouped(self, q_unit, k: int, n_cus, groups: MaskGroups):
         """``search`` under a mask per query, each query exact over its own mask's rows.
 
@@ -1725,6 +1735,11 @@ class HbmIndexShard:
           e4m3(q) . e4m3(x), with the MFMA chain of the single-mask scan, bit for bit alike.
           (A chunk of two to four large disjoint masks whose queries grouping would spread
           over one more query block stays with the next route: _loop_keeps_chunk.)
+        * A GPU fp8 shard of FP8_LARGE_K_MIN_ROWS visible rows or more at 32 < k <= 128 with
+          GROUP_SCAN_MIN_GROUPS masks or more: per chunk, the grouped list scan as the seed
+          passes and the grouped emitting e4m3 scan (_search_group_chunk_large_k), under the
+          same _loop_keeps_chunk rule.  A chunk whose candidates overflow LARGE_K_CAP goes to
+          the next route.
         * Everything else: one ``_search_masked`` per mask over its queries, scattered back.
           Those are the existing routes, exact as they stand: a CPU shard, k > 128, other
           widths and small fp8 shards at k > 32 score float(q) . float(x) (fp8:
@@ -1756,7 +1771,8 @@ class HbmIndexShard:
                 s, i = self._search_masked(q_unit[idx], k, n_cus, groups.masks[g])
                 out_s[idx], out_i[idx] = s, i.to(torch.int32)
 
-        if self._group_scan_serves(k, groups):
+        large_k = self._group_large_k_serves(k, groups)
+        if large_k or self._group_scan_serves(k, groups):
             q = q_unit.to(torch.bfloat16).contiguous()
             if self.dtype == "fp8":
                 # e4m3 bytes, once per search (as _search_filtered quantises them per mask)
@@ -1768,7 +1784,14 @@ class HbmIndexShard:
                 if self._loop_keeps_chunk(ch, k):
                     loop(ch["groups"][0], sum(ch["groups"]))
                     continue
-                s, i = self._search_group_chunk(q[ch["idx"]], k, groups, ch, n_cus)
+                if large_k:
+                    res = self._search_group_chunk_large_k(q[ch["idx"]], k, groups, ch, n_cus)
+                    if res is None:     # candidates past LARGE_K_CAP: the parent's route, exact
+                        loop(ch["groups"][0], sum(ch["groups"]))
+                        continue
+                    s, i = res
+                else:
+                    s, i = self._search_group_chunk(q[ch["idx"]], k, groups, ch, n_cus)
                 out_s[ch["idx"]], out_i[ch["idx"]] = s, i
             return out_s, out_i
         loop(0, len(groups))
@@ -1787,14 +1810,26 @@ class HbmIndexShard:
     # 100M rows, 512 queries, disjoint 1 % masks, 2 / 4 groups: 1.571 / 2.819 against the loop's
     # 1.042 / 1.898 ms at 1024, 1.019 / 1.702 against 0.741 / 1.361 at 384), so the same
     # constants serve it; 8 groups and the tile floor are unmeasured on fp8.
+    #
+    # At 32 < k <= 128 (the grouped emitting scan of an fp8 shard; README, round 16) the same
+    # case was measured at k = 100 with the scan forced, 100M rows, 512 queries, disjoint 1 %
+    # masks, 2 / 4 groups, scan against loop (its min-max): at 1024 2.306 against 2.125
+    # (2.124-2.128) and 3.704 against 3.676 (3.653-3.680) ms, behind and tied, so the rule holds
+    # there; at 384 1.798 against 1.904 (1.893-1.915) and 2.584 against 3.406 (3.401-3.419),
+    # ahead by more than the loop's spread (at this k a masked search is three launches and a
+    # select, and the scan saves them per mask), so 384 is exempt.  256 / 512 / 768 are
+    # unmeasured and keep the rule: the loop is what the parent of that change did everywhere.
     GROUP_LOOP_MAX_GROUPS = 4
     GROUP_LOOP_MIN_TILES = 16384
+    GROUP_LOOP_LARGE_K_SCAN_DIMS = (384,)
 
     def _loop_keeps_chunk(self, ch: dict, k: int) -> bool:
         from ..ops._ext import hip
 
         live = ch["live"]
         if live is None or not 2 <= len(ch["nq_of"]) <= self.GROUP_LOOP_MAX_GROUPS:
+            return False
+        if k > 32 and self.dim in self.GROUP_LOOP_LARGE_K_SCAN_DIMS:
             return False
         # queries per block of the scans: 256 on fp8 (the rule can then hold above 256 queries
         # only), topk_geometry's on bf16
@@ -1864,6 +1899,68 @@ class HbmIndexShard:
     # all-ones mask 21.6 -> 18.1 ms, documents 10 % 3.13 -> 2.73, uniform 1 % 8.51 -> 8.72 (the
     # extra launch where the lists hardly fill); same T, same candidates (profiles/r11_filter_largek/)
     FILTER_LARGE_K_COARSE = 16
+
+    def _search_group_chunk_large_k(self, q8, k: int, groups: MaskGroups, ch: dict, n_cus,
+                                    seed: bool = True):
+        """_filtered_large_k_fp8 under a mask per query, over one chunk's queries (``q8``: their
+        e4m3 bytes, quantised once per search by _search_grouped): the same grid, the grouped
+        e4m3 list scan (index_filter_group_fp8.hip) as the seed pass at kmax 32 over every
+        FILTER_LARGE_K_STRIDE-th tile of the union's list -- itself seeded at kmax 16 and stride
+        x FILTER_LARGE_K_COARSE from SEED_MIN_ROWS rows on -- and the grouped emitting scan
+        (index_emit_group_fp8.hip) over the whole list.  A query's seed candidates are rows of
+        its own mask only, so T (filter_large_k_threshold_ulp: all three kernels run one MFMA
+        chain) is a lower bound on its k-th best score under its own mask.  ``seed=False``:
+        T = -inf.  Returns None when a query's candidates overflow LARGE_K_CAP (the flag is
+        read once per chunk); the caller then answers the chunk's groups one mask at a time."""
+        from ..ops import kernels as K
+        from ..ops._ext import hip, stream_handle
+
+        h, dev = hip(), self.device
+        NQ = q8.shape[0]
+        n = min(groups.visible, self.visible)
+        out_s = torch.empty(NQ, k, device=dev)
+        out_i = torch.empty(NQ, k, dtype=torch.int32, device=dev)
+        if n <= 0:
+            return out_s.fill_(-math.inf), out_i.fill_(-1)
+        if n_cus is None:
+            n_cus = self._n_cus()
+        tile_slots = math.ceil(n / (TILE_ROWS * self.FILTER_MIN_TILES))
+        n_qblk = math.ceil(NQ / 256)
+        n_rblk = max(1, min(tile_slots, max(1, round(n_cus / n_qblk))))
+        mask8, qgroup, tiles, n_live = ch["mask8"], ch["qgroup"], ch["tiles"], ch["n_live"]
+        if seed:
+            cs = torch.empty(NQ, n_rblk * 2 * 32, device=dev)
+            ci = torch.empty(NQ, n_rblk * 2 * 32, dtype=torch.int32, device=dev)
+            T0 = None
+            if self.FILTER_LARGE_K_COARSE > 1 and n >= self.SEED_MIN_ROWS:
+                # the seed pass's own seed: a subset of its sample, so T is unchanged
+                c0 = torch.empty(NQ, n_rblk * 2 * 16, device=dev)
+                i0 = torch.empty(NQ, n_rblk * 2 * 16, dtype=torch.int32, device=dev)
+                K.index_scan_filter_group_fp8(
+                    self.rows, n, mask8, qgroup, tiles, n_live, q8, 16, n_rblk, c0, i0, None,
+                    self.FILTER_LARGE_K_STRIDE * self.FILTER_LARGE_K_COARSE, self.scan_xcd)
+                T0 = filter_large_k_threshold_ulp(c0, k)
+            K.index_scan_filter_group_fp8(self.rows, n, mask8, qgroup, tiles, n_live, q8, 32,
+                                          n_rblk, cs, ci, T0, self.FILTER_LARGE_K_STRIDE,
+                                          self.scan_xcd)
+            T = filter_large_k_threshold_ulp(cs, k)
+        else:
+            T = torch.full((NQ,), -math.inf, device=dev)
+        cap = self.LARGE_K_CAP
+        es = torch.empty(NQ, cap, device=dev)
+        ei = torch.empty(NQ, cap, dtype=torch.int32, device=dev)
+        cnt = torch.empty(NQ, dtype=torch.int32, device=dev)
+        ovf = torch.zeros(1, dtype=torch.int32, device=dev)
+        K.index_scan_emit_group_fp8(self.rows, n, mask8, qgroup, tiles, n_live, q8, T, es, ei,
+                                    cnt, cap, n_rblk, self.scan_xcd)
+        h.topk_select_counted(es.data_ptr(), ei.data_ptr(), cnt.data_ptr(), cap, NQ, 128, k,
+                              out_s.data_ptr(), out_i.data_ptr(), ovf.data_ptr(),
+                              stream_handle(dev), gate=0, reset_ovf=False)
+        out_s.mul_(1.0 / (FP8_SCALE * FP8_SCALE))   # (-inf stays -inf)
+        self._filter_large_k_last = (cnt, ovf)   # candidate counts / overflow flag (tests)
+        if int(ovf.item()):
+            return None
+        return out_s, out_i
 
     def _mq_filter_form(self, NQ: int):
         """(sets, rsplit) of the masked emitting scan: _mq_form's, except that at D = 384 below

@@ -594,6 +594,71 @@ def index_scan_emit_fp8(rows_u8: torch.Tensor, n_valid: int, mask_words: torch.T
                               stream_handle(rows_u8.device), xcd, _ptr(gate), bool(zero_cnt))
 
 
+def index_scan_emit_group_fp8(rows_u8: torch.Tensor, n_valid: int, mask8: torch.Tensor,
+                              qgroup: torch.Tensor, tiles: torch.Tensor, n_live: torch.Tensor,
+                              q_e4m3: torch.Tensor, thr: torch.Tensor, cand_s: torch.Tensor,
+                              cand_i: torch.Tensor, cand_n: torch.Tensor, cap: int, n_rblk: int,
+                              xcd: int = 1, gate: torch.Tensor | None = None,
+                              zero_cnt: bool = True) -> None:
+    """``index_scan_emit_fp8`` under a mask per query (index_emit_group_fp8.hip): ``mask8`` int64
+    [n_words, 8] and ``qgroup`` int32 [NQ] as in ``index_scan_filter_group_fp8``, ``tiles`` /
+    ``n_live`` ``filter_tiles`` of the OR of the eight slots.  Query q's candidates are those of
+    ``index_scan_emit_fp8`` under slot ``qgroup[q]``'s words: every row that slot allows below
+    ``n_valid`` whose raw score, bit for bit the list scans', lies above ``thr[q]``.
+    ``cand_s`` / ``cand_i`` [NQ, cap], ``cand_n`` [NQ] (may exceed ``cap``; nothing is written at
+    or past it), ``zero_cnt`` and ``gate`` as there."""
+    if rows_u8.dtype != torch.uint8 or q_e4m3.dtype != torch.uint8:
+        # (a bf16 slab of the same width would be read as twice as many e4m3 rows)
+        raise ValueError("index_scan_emit_group_fp8: rows and queries are e4m3 bytes (uint8), "
+                         f"got {rows_u8.dtype} / {q_e4m3.dtype}")
+    _chk(rows_u8, torch.uint8, "rows_u8", 2)
+    _chk(q_e4m3, torch.uint8, "q_e4m3", 2)
+    _chk(mask8, torch.int64, "mask8", 2)
+    _chk(qgroup, torch.int32, "qgroup", 1)
+    _chk(tiles, torch.int32, "tiles", 1)
+    _chk(n_live, torch.int32, "n_live", 1)
+    if thr is None or thr.dtype != torch.float32:
+        raise ValueError("index_scan_emit_group_fp8: thr is a float32 tensor, one threshold per "
+                         "query")
+    _chk(thr, torch.float32, "thr", 1)
+    _chk(cand_s, torch.float32, "cand_s")
+    _chk(cand_i, torch.int32, "cand_i")
+    _chk(cand_n, torch.int32, "cand_n", 1)
+    D = rows_u8.shape[1]
+    NQ = q_e4m3.shape[0]
+    n_valid, n_rblk, cap = int(n_valid), int(n_rblk), int(cap)
+    if D not in FILTER_FP8_DIMS or q_e4m3.shape[1] != D:
+        raise ValueError(f"index_scan_emit_group_fp8: rows must be {FILTER_FP8_DIMS} wide, "
+                         "queries alike")
+    if n_rblk < 1 or cap < 1 or n_valid < 0 or n_live.numel() < 1:
+        raise ValueError("index_scan_emit_group_fp8: n_rblk >= 1, cap >= 1, n_valid >= 0")
+    if mask8.shape[1] != MASK_GROUPS or not mask8.is_contiguous():
+        raise ValueError("index_scan_emit_group_fp8: mask8 must be contiguous "
+                         f"[n_words, {MASK_GROUPS}]")
+    if qgroup.numel() != NQ:
+        raise ValueError("index_scan_emit_group_fp8: qgroup must hold one group per query")
+    n_tiles = (n_valid + 63) // 64
+    # every tile the list can name lies inside the row slab and has its eight mask words
+    if n_tiles * 64 > rows_u8.shape[0] or n_tiles > mask8.shape[0] or n_tiles > tiles.numel():
+        raise ValueError("index_scan_emit_group_fp8: rows / mask8 / tile list shorter than "
+                         "n_valid")
+    if thr.numel() != NQ:
+        raise ValueError("index_scan_emit_group_fp8: one threshold per query")
+    if cand_n.numel() < NQ:
+        raise ValueError("index_scan_emit_group_fp8: cand_n shorter than the batch")
+    if cand_s.numel() < NQ * cap or cand_i.numel() < NQ * cap:
+        raise ValueError("index_scan_emit_group_fp8: candidate workspace too small")
+    if gate is not None:
+        _chk(gate, torch.int32, "gate", 1)
+        if gate.numel() < 1:
+            raise ValueError("index_scan_emit_group_fp8: gate is one int32 flag")
+    hip().index_scan_emit_group_fp8(_ptr(rows_u8), n_valid, D, _ptr(tiles), _ptr(n_live),
+                                    _ptr(mask8), _ptr(qgroup), n_rblk, _ptr(q_e4m3), NQ,
+                                    _ptr(thr), _ptr(cand_s), _ptr(cand_i), _ptr(cand_n), cap,
+                                    stream_handle(rows_u8.device), xcd, _ptr(gate),
+                                    bool(zero_cnt))
+
+
 def tombstone_rows(rows_list: torch.Tensor, n_valid: int, dead_words: torch.Tensor,
                    slab: torch.Tensor, slab2: torch.Tensor | None = None) -> None:
     """Tombstone the listed rows (index_delete.hip): zeros over each row of ``slab`` (and of

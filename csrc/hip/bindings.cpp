@@ -110,6 +110,12 @@ int symb_index_scan_emit_fp8(const void* X, int n_valid, int D, const int* tiles
                              const int* n_live, const void* mask, int n_rblk, const void* Q,
                              int NQ, const float* thr, float* cand_s, int* cand_i, int* cand_n,
                              int cap, hipStream_t st, int xcd, const int* gate, int zero_cnt);
+// ... under a mask per query group (index_emit_group_fp8.hip)
+int symb_index_scan_emit_group_fp8(const void* X, int n_valid, int D, const int* tiles,
+                                   const int* n_live, const void* mask8, const int* qgroup,
+                                   int n_rblk, const void* Q, int NQ, const float* thr,
+                                   float* cand_s, int* cand_i, int* cand_n, int cap,
+                                   hipStream_t st, int xcd, const int* gate, int zero_cnt);
 // the masked emitting scan (index_mq_filter.hip)
 int symb_index_scan_mq_filter(const void* X, int n_valid, const int* tiles, const int* n_live,
                               const void* mask, int n_rblk, const void* Q, int NQ,
@@ -1004,6 +1010,21 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("mask"), py::arg("n_rblk"), py::arg("Q"), py::arg("NQ"), py::arg("thr"),
      py::arg("cand_s"), py::arg("cand_i"), py::arg("cand_n"), py::arg("cap"), py::arg("stream"),
      py::arg("xcd") = 1, py::arg("gate") = 0, py::arg("zero_cnt") = true);
+  m.def("index_scan_emit_group_fp8", [](uptr X, int n_valid, int D, uptr tiles, uptr n_live,
+                                        uptr mask8, uptr qgroup, int n_rblk, uptr Q, int NQ,
+                                        uptr thr, uptr cand_s, uptr cand_i, uptr cand_n, int cap,
+                                        uptr st, int xcd, uptr gate, bool zero_cnt) {
+    check(symb_index_scan_emit_group_fp8(P<void>(X), n_valid, D, P<const int>(tiles),
+                                         P<const int>(n_live), P<void>(mask8),
+                                         P<const int>(qgroup), n_rblk, P<void>(Q), NQ,
+                                         P<const float>(thr), P<float>(cand_s), P<int>(cand_i),
+                                         P<int>(cand_n), cap, S(st), xcd, P<const int>(gate),
+                                         zero_cnt ? 1 : 0),
+          "index_scan_emit_group_fp8");
+  }, py::arg("X"), py::arg("n_valid"), py::arg("D"), py::arg("tiles"), py::arg("n_live"),
+     py::arg("mask8"), py::arg("qgroup"), py::arg("n_rblk"), py::arg("Q"), py::arg("NQ"),
+     py::arg("thr"), py::arg("cand_s"), py::arg("cand_i"), py::arg("cand_n"), py::arg("cap"),
+     py::arg("stream"), py::arg("xcd") = 1, py::arg("gate") = 0, py::arg("zero_cnt") = true);
   m.def("tombstone_rows", [](uptr rows, int n, int n_valid, uptr slab0, int es0, uptr slab1,
                              int es1, int D, uptr dead, uptr st) {
     check(symb_tombstone_rows(P<const int>(rows), n, n_valid, P<void>(slab0), es0, P<void>(slab1),

@@ -1,43 +1,51 @@
-// The emitting e4m3 scan under a row mask: index_scan_filter_fp8_kernel (index_filter_fp8.hip) with
-// its per-lane register top-k replaced by the threshold emission of index_scan_mq_filter_kernel
-// (index_mq_filter.hip).  It serves fp8 shards at 32 < k <= 128, masked, tombstoned or (under an
-// all-ones mask) plain, where no register list fits: every ALLOWED row scoring above the query's
-// threshold (a lower bound on its final k-th allowed score) is appended to the query's candidate
-// buffer, and the radix select takes the top k.
+// The emitting e4m3 scan under a row mask PER QUERY: index_scan_emit_fp8_kernel
+// (index_emit_fp8.hip) with the tile's mask word a per-query value, the step
+// index_scan_filter_group_fp8_kernel (index_filter_group_fp8.hip) takes from the masked e4m3 list
+// scan.  It serves fp8 shards at 32 < k <= 128 when the queries of one 256-query block fall into
+// up to MASK_GROUPS = 8 filters: one scan of the union's live tiles appends, for every query,
+// each row ALLOWED UNDER THAT QUERY'S OWN MASK that scores above the query's threshold, and the
+// radix select takes the top k.
 //
-// From index_scan_filter_fp8_kernel, unchanged: 4 waves, 64 queries per wave as two 32-query
-// B-fragment sets resident in AGPRs, v_mfma_f32_32x32x64_f8f6f4 through Fp8Chain (the same chain,
-// so a row scores bit for bit what the list scan gives it: the search's threshold is a list-scan
-// score and carries no margin), the Fp8Swz LDS image, the LDS-DMA ring with counted vmcnt and a raw
-// barrier at Fp8Cfg<D>'s depth, the workgroup's slice of the live-tile list with n_live read on the
-// device, tile_ptr / half_row clamping every list read to the slice's last interval, the batch of
-// NS scalar loads in the prologue and the scalar state one interval ahead, live_word, mask_rows.
-// Without the register lists four fragment reads are in flight at every width (the list scan
-// keeps three at 1024).  No stride: the seed passes of the search stay the list scan.
+// Kept from index_scan_emit_fp8_kernel, unchanged: 4 waves, 64 queries per wave as two
+// AGPR-resident 32-query B-fragment sets, Fp8Chain / fp8_prologue with four fragment reads in
+// flight at every width (so a row scores bit for bit what it scores there and in the list scans:
+// the search's threshold is a list-scan score and carries no margin), the Fp8Swz LDS image, the
+// Fp8Cfg<D> ring with counted vmcnt and the raw barrier, the slice of the live-tile list with
+// n_live read on the device, tile_ptr / half_row clamped to the slice's last interval, the batch
+// of NS scalar tile loads in the prologue, thr[NQ] in raw units (+inf for padding queries), the
+// per-wave LDS stage behind the ring and its flush through atomicAdd(cand_n + q, 1) with nothing
+// written at or past cap, the gate and the gated zeroing of cand_n.
 //
-// From index_scan_mq_filter_kernel: the fixed per-query threshold thr[NQ] (raw units, S^2 *
-// cosine), the per-wave LDS stage of (raw score, physical row, query-in-wave) behind the ring
-// (mq::STW entries, flushed before a 64-lane ballot could overflow it), the flush that takes
-// slot = atomicAdd(cand_n + q, 1) and stores only below cap.  A sub-tile whose 32 mask bits are 0
-// is not tested at all; queries at or past NQ (clamped for loading) hold thr = +inf and never
-// emit, their counters do not exist.
+// Taken from index_scan_filter_group_fp8_kernel and mask_group.h: mask8 (uint64 [n_words][8]),
+// qgroup (int32 [NQ], & 7, clamped like the fragments), a lane's two group ids in one VGPR, the
+// s_load_dwordx16 of the NEXT tile's words issued at the barrier and waited for at the
+// interval's end with the tile indices (that kernel's placement below kmax 32: there are no
+// register lists here, so no update fills the SGPR file), pick2 cutting the two picked words at
+// n_valid, mask_rows with a select per set and the wave-vote all-ones shortcut.
+//
+// What is new: the single-mask kernel skips a sub-tile whose 32 bits are 0 by a wave-uniform
+// return.  Here the bits are per lane while the emission holds ballots and a wave-uniform stage
+// count, so the skip is a wave VOTE -- no lane has a bit in b0 | b1 -- and never a per-lane
+// exit.  A tile of the union may be dead for every query of one wave and live for another
+// wave's; a lane whose own bits are 0 inside a live sub-tile holds -inf in all sixteen
+// accumulators of that set, and the test is the strict >, so even thr = -inf emits nothing for
+// it: a query only ever emits rows of its own mask.
+//
+// Register budget: profiles/r16_group_emit_fp8/resource_usage.md.
 #include "fp8_emit.h"
+#include "mask_group.h"
 
 namespace symb {
 
-// X: [>= round_up(n_valid, 64), D] e4m3 rows (scale S); Q: [NQ, D] e4m3 queries (scale S).
-// tiles / n_live_p: filter_tiles' output for `mask` at this n_valid; mask: the words it read.
-// thr[NQ] (required): per-query lower bounds on the final k-th ALLOWED score, raw units.
-// cand_s / cand_i: [NQ][cap] raw scores / physical rows; cand_n[NQ]: candidates each query emitted
-// (may exceed cap; nothing is written at or past cap, and the select kernel raises the overflow
-// flag).  gate (optional): run only if *gate != 0.
+// X / Q / thr_in / cand_* / cap / gate: as index_scan_emit_fp8_kernel.  mask8 / qgroup: as
+// index_scan_filter_group_fp8_kernel; tiles / n_live_p: filter_tiles of the OR of the slots.
 template <int D, int NS, int SUBS, int AUX>
-__global__ __launch_bounds__(256, 1) void index_scan_emit_fp8_kernel(
+__global__ __launch_bounds__(256, 1) void index_scan_emit_group_fp8_kernel(
     const uint8_t* __restrict__ X, int n_valid, const int* __restrict__ tiles,
-    const int* __restrict__ n_live_p, const uint64_t* __restrict__ mask,
-    const uint8_t* __restrict__ Q, int NQ, int n_qblk, int xcd, const float* __restrict__ thr_in,
-    float* __restrict__ cand_s, int* __restrict__ cand_i, int* __restrict__ cand_n, int cap,
-    const int* __restrict__ gate) {
+    const int* __restrict__ n_live_p, const uint64_t* __restrict__ mask8,
+    const int* __restrict__ qgroup, const uint8_t* __restrict__ Q, int NQ, int n_qblk, int xcd,
+    const float* __restrict__ thr_in, float* __restrict__ cand_s, int* __restrict__ cand_i,
+    int* __restrict__ cand_n, int cap, const int* __restrict__ gate) {
   if (gate != nullptr && *gate == 0) return;   // (grid-uniform, before any barrier)
   constexpr int CPR = D / 16, SUB = 32, TR = 32 * SUBS, NW = 4;
   constexpr int IPE = 64 / TR;                     // barrier intervals per list entry
@@ -70,8 +78,7 @@ __global__ __launch_bounds__(256, 1) void index_scan_emit_fp8_kernel(
   const int slice_len = max(min(per, n_live - slice_begin), 0);          // entries walked
   const int n_iv = __builtin_amdgcn_readfirstlane(slice_len * IPE);      // barrier intervals
   // interval iv (clamped to the last one) -> its entry's position in the list / its first row
-  // within that entry's tile.  Called with n_iv > 0 only.  (readfirstlane: the scalar loads take
-  // an SGPR address, and the compiler may select the clamp of a constant iv on the vector ALU)
+  // within that entry's tile.  Called with n_iv > 0 only.  (readfirstlane: index_emit_fp8.hip)
   auto tile_ptr = [&](int iv) {
     return tiles + slice_begin + __builtin_amdgcn_readfirstlane(min(iv, n_iv - 1) / IPE);
   };
@@ -92,8 +99,12 @@ __global__ __launch_bounds__(256, 1) void index_scan_emit_fp8_kernel(
   // padding queries never emit: their counters do not exist
   const float thr0 = query0 < NQ ? thr_in[query0] : INFINITY;
   const float thr1 = query1 < NQ ? thr_in[query1] : INFINITY;
-  // consume the threshold loads before any LDS-DMA is in flight (index_mq.hip)
-  asm volatile("" ::"v"(thr0), "v"(thr1));
+  // the lane's two mask groups in one register, set 0's in bits 0-2 and set 1's in bits 4-6
+  // (padded lanes take the last query's, like its fragments)
+  const int grps = (qgroup[min(query0, NQ - 1)] & (MASK_GROUPS - 1)) |
+                   ((qgroup[min(query1, NQ - 1)] & (MASK_GROUPS - 1)) << 4);
+  // consume the threshold and group loads before any LDS-DMA is in flight (index_mq.hip)
+  asm volatile("" ::"v"(thr0), "v"(thr1), "v"(grps));
   // per-piece source offsets within an interval, as in index_scan_fp8_kernel
   constexpr int RPS = (NW * 64) % CPR == 0 ? NW * 64 / CPR : 0;   // rows per piece step
   constexpr int GP = (G == 16 && RPS > 0 && 16 % RPS == 0 && LOADS % (16 / RPS) == 0)
@@ -123,17 +134,29 @@ __global__ __launch_bounds__(256, 1) void index_scan_emit_fp8_kernel(
         voff[m * 2 + j] = (uint32_t)(r * D + (Swz::phys(4 * m + 2 * h + j, r) << 4));
   }
 
-  // row of accumulator register r within the 32-row sub-tile = 4 h + acc_reg_row(r), for
-  // both query sets; bits: the sub-tile's 32 mask bits (wave-uniform), bit j = row j allowed
-  auto mask_rows = [&](f32x16& a0, f32x16& a1, uint32_t bits) {
-    if (bits != 0xffffffffu) {
-      const uint32_t lbits = bits >> (4 * h);
+  // the lane's two words out of a tile's eight, cut at n_valid
+  auto pick2 = [&](const u32x16& w8, int tile, uint64_t& w0, uint64_t& w1) {
+    const uint64_t cut = live_word(~0ull, tile, n_valid);
+    // (opaque: the fourteen compares against the group ids are loop invariants, and hoisted
+    // out of the interval loop their masks are 28 SGPRs held across it)
+    // (pick_word's plain form: the sequenced one changes no register figure here, the SGPR
+    // file is not full without the register lists)
+    int g = grps;
+    asm volatile("" : "+v"(g));
+    w0 = pick_word(w8, g & 15) & cut;
+    w1 = pick_word(w8, g >> 4) & cut;
+  };
+  // row of accumulator register r within the 32-row sub-tile = 4 h + acc_reg_row(r), for both
+  // query sets; b0 / b1: the sub-tile's 32 mask bits of the lane's set 0 / set 1 query, bit j =
+  // row j allowed.  The shortcut is a wave vote over both sets (index_filter_group_fp8.hip).
+  auto mask_rows = [&](f32x16& a0, f32x16& a1, uint32_t b0, uint32_t b1) {
+    if (__any(b0 != 0xffffffffu || b1 != 0xffffffffu)) {
+      const uint32_t l0 = b0 >> (4 * h), l1 = b1 >> (4 * h);
 #pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (!((lbits >> acc_reg_row<true>(r)) & 1u)) {
-          a0[r] = -INFINITY;
-          a1[r] = -INFINITY;
-        }
+      for (int r = 0; r < 16; ++r) {
+        if (!((l0 >> acc_reg_row<true>(r)) & 1u)) a0[r] = -INFINITY;
+        if (!((l1 >> acc_reg_row<true>(r)) & 1u)) a1[r] = -INFINITY;
+      }
     }
   };
 
@@ -176,10 +199,12 @@ __global__ __launch_bounds__(256, 1) void index_scan_emit_fp8_kernel(
       }
     }
   };
-  // one 32-row sub-tile at physical row prow0 whose 32 mask bits are ``bits`` (wave-uniform)
-  auto emit = [&](f32x16& a0, f32x16& a1, int prow0, uint32_t bits) {
-    if (bits == 0u) return;   // no allowed row: nothing to test (the chain ran all the same)
-    mask_rows(a0, a1, bits);
+  // one 32-row sub-tile at physical row prow0; b0 / b1: its 32 mask bits for the LANE's two
+  // queries.  Every branch here is a wave vote: emit_set holds ballots and the wave-uniform nst.
+  auto emit = [&](f32x16& a0, f32x16& a1, int prow0, uint32_t b0, uint32_t b1) {
+    // no query of this wave has an allowed row here: nothing to test (the chain ran all the same)
+    if (!__builtin_amdgcn_ballot_w64((b0 | b1) != 0u)) return;
+    mask_rows(a0, a1, b0, b1);
     const float mx0 = fp8_max16(a0), mx1 = fp8_max16(a1);
     if (__builtin_amdgcn_ballot_w64(mx0 > thr0 || mx1 > thr1)) {
       // cold path: per-lane values come from an opaque copy made here, so nothing it derives can
@@ -192,8 +217,10 @@ __global__ __launch_bounds__(256, 1) void index_scan_emit_fp8_kernel(
     }
   };
 
+  // Scalar state as index_scan_emit_fp8_kernel; w0 / w1 are the LANE's mask words of interval
+  // t's tile for its two queries (VGPR pairs).
   int t_cur = 0, t_nxt = 0, t_pf = 0;
-  uint64_t w_cur = 0;
+  uint64_t w0 = 0, w1 = 0;
   if (n_iv > 0) {
     // tiles of intervals 0 .. NS - 1 (each clamped to the slice): 0 .. NS - 2 fill the ring now,
     // NS - 1 is interval 0's prefetch
@@ -204,9 +231,10 @@ __global__ __launch_bounds__(256, 1) void index_scan_emit_fp8_kernel(
     t_cur = tp[0];
     t_nxt = tp[1];
     t_pf = tp[NS - 1];
-    sload_u64(w_cur, mask + t_cur);
-    swait(t_cur, t_nxt, w_cur);
-    w_cur = live_word(w_cur, t_cur, n_valid);
+    u32x16 w8;
+    sload_mask8(w8, mask8 + (size_t)MASK_GROUPS * t_cur);
+    swait_mask8(t_cur, t_nxt, w8);
+    pick2(w8, t_cur, w0, w1);
 #pragma unroll
     for (int p = 0; p < NS - 1; ++p) {
       const int row_base = tp[p] * 64 + half_row(p);
@@ -222,10 +250,10 @@ __global__ __launch_bounds__(256, 1) void index_scan_emit_fp8_kernel(
     __builtin_amdgcn_s_barrier();
     // next interval's scalar state (waited for at the end of this interval)
     int n_nxt, n_pf;
-    uint64_t n_w;
+    u32x16 n_w8;
     sload_i32(n_nxt, tile_ptr(t + 2));
     sload_i32(n_pf, tile_ptr(t + NS));
-    sload_u64(n_w, mask + t_nxt);
+    sload_mask8(n_w8, mask8 + (size_t)MASK_GROUPS * t_nxt);
 
     const uint32_t tbase = lds_smem + (uint32_t)((t % NS) * TILE_BYTES);
     const int h0 = half_row(t);
@@ -247,32 +275,18 @@ __global__ __launch_bounds__(256, 1) void index_scan_emit_fp8_kernel(
         fp8_prologue<0, PF, R, G>(lo, hi, voff, base + SUB_BYTES);
       // (reads of the asm MFMA results stay below the chain-end s_nops: index_i8.hip emit)
       asm volatile("" : "+v"(acc0), "+v"(acc1));
-      emit(acc0, acc1, row0 + sub * SUB, (uint32_t)(w_cur >> (h0 + sub * SUB)));
+      emit(acc0, acc1, row0 + sub * SUB, (uint32_t)(w0 >> (h0 + sub * SUB)),
+           (uint32_t)(w1 >> (h0 + sub * SUB)));
     }
 
-    swait(n_nxt, n_pf, n_w);
+    swait_mask8(n_nxt, n_pf, n_w8);
+    pick2(n_w8, t_nxt, w0, w1);
     t_cur = t_nxt;
     t_nxt = n_nxt;
     t_pf = n_pf;
-    w_cur = live_word(n_w, t_cur, n_valid);
   }
   if (nst) flush();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tail prefetches and emissions
-}
-
-// cand_n[0 .. NQ) = 0 under the scan's gate: with *gate == 0 the counters keep what they held
-__global__ void emit_fp8_zero_kernel(int* __restrict__ cand_n, int NQ,
-                                     const int* __restrict__ gate) {
-  if (*gate == 0) return;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < NQ) cand_n[i] = 0;
-}
-
-int emit_fp8_zero_counts(int* cand_n, int NQ, const int* gate, hipStream_t st) {
-  if (gate == nullptr) return (int)hipMemsetAsync(cand_n, 0, sizeof(int) * (size_t)NQ, st);
-  hipLaunchKernelGGL(emit_fp8_zero_kernel, dim3((NQ + 255) / 256), dim3(256), 0, st, cand_n, NQ,
-                     gate);
-  return 0;
 }
 
 }  // namespace symb
@@ -280,32 +294,32 @@ int emit_fp8_zero_counts(int* cand_n, int NQ, const int* gate, hipStream_t st) {
 using namespace symb;
 
 template <int D, int AUX>
-static int launch_emit_fp8(const void* X, int n_valid, const int* tiles, const int* n_live,
-                           const void* mask, int n_rblk, const void* Q, int NQ, int n_qblk,
-                           int xcd, const float* thr, float* cs, int* ci, int* cn, int cap,
-                           hipStream_t st, const int* gate) {
+static int launch_emit_group_fp8(const void* X, int n_valid, const int* tiles, const int* n_live,
+                                 const void* mask8, const int* qgroup, int n_rblk, const void* Q,
+                                 int NQ, int n_qblk, int xcd, const float* thr, float* cs, int* ci,
+                                 int* cn, int cap, hipStream_t st, const int* gate) {
   constexpr int SUBS = Fp8Cfg<D>::SUBS, NS = Fp8Cfg<D>::NS;
   constexpr int lds = NS * 32 * SUBS * D + 4 * mq::STAGE_BYTES;
-  set_max_lds<index_scan_emit_fp8_kernel<D, NS, SUBS, AUX>>(lds);
-  hipLaunchKernelGGL((index_scan_emit_fp8_kernel<D, NS, SUBS, AUX>), dim3(n_rblk * n_qblk),
+  set_max_lds<index_scan_emit_group_fp8_kernel<D, NS, SUBS, AUX>>(lds);
+  hipLaunchKernelGGL((index_scan_emit_group_fp8_kernel<D, NS, SUBS, AUX>), dim3(n_rblk * n_qblk),
                      dim3(256), lds, st, (const uint8_t*)X, n_valid, tiles, n_live,
-                     (const uint64_t*)mask, (const uint8_t*)Q, NQ, n_qblk, xcd, thr, cs, ci, cn,
-                     cap, gate);
+                     (const uint64_t*)mask8, qgroup, (const uint8_t*)Q, NQ, n_qblk, xcd, thr, cs,
+                     ci, cn, cap, gate);
   return (int)hipGetLastError();
 }
 
-// X / Q / tiles / n_live / mask: as symb_index_scan_filter_fp8.  thr[NQ] (required), cand_s /
-// cand_i [NQ][cap], cand_n[NQ]: as symb_index_scan_mq_filter, in raw units (S^2 * cosine).  The
-// grid is n_rblk row slots x ceil(NQ / 256) query blocks, the slots sharing the live tiles evenly.
-// zero_cnt = 0 appends to cand_n instead of zeroing it; with a gate the zeroing is gated too, so
-// a closed gate leaves every buffer as it was.
-int symb_index_scan_emit_fp8(const void* X, int n_valid, int D, const int* tiles,
-                             const int* n_live, const void* mask, int n_rblk, const void* Q,
-                             int NQ, const float* thr, float* cand_s, int* cand_i, int* cand_n,
-                             int cap, hipStream_t st, int xcd, const int* gate, int zero_cnt) {
+// As symb_index_scan_emit_fp8 (index_emit_fp8.hip), with the mask a word per group as in
+// symb_index_scan_filter_group_fp8: mask8 [n_words][8] 64-bit words, qgroup [NQ] ints (low three
+// bits), tiles / n_live symb_filter_tiles' output for the OR of the eight slots at this n_valid.
+int symb_index_scan_emit_group_fp8(const void* X, int n_valid, int D, const int* tiles,
+                                   const int* n_live, const void* mask8, const int* qgroup,
+                                   int n_rblk, const void* Q, int NQ, const float* thr,
+                                   float* cand_s, int* cand_i, int* cand_n, int cap,
+                                   hipStream_t st, int xcd, const int* gate, int zero_cnt) {
   if (NQ <= 0) return 0;
   if (n_rblk <= 0 || n_valid < 0 || thr == nullptr || cap <= 0) return -1;
-  if (!X || !Q || !tiles || !n_live || !mask || !cand_s || !cand_i || !cand_n) return -1;
+  if (!X || !Q || !tiles || !n_live || !mask8 || !qgroup || !cand_s || !cand_i || !cand_n)
+    return -1;
   if (D != 256 && D != 384 && D != 512 && D != 768 && D != 1024) return -1;
   if (zero_cnt) {
     const int e = emit_fp8_zero_counts(cand_n, NQ, gate, st);
@@ -313,8 +327,8 @@ int symb_index_scan_emit_fp8(const void* X, int n_valid, int D, const int* tiles
   }
   const int n_qblk = (NQ + 255) / 256;
   const int aux = n_qblk == 1 ? 2 : 0;   // non-temporal when each index row is read by one block
-#define SYMB_E(D_) (aux ? launch_emit_fp8<D_, 2>(X, n_valid, tiles, n_live, mask, n_rblk, Q, NQ, n_qblk, xcd, thr, cand_s, cand_i, cand_n, cap, st, gate) \
-                        : launch_emit_fp8<D_, 0>(X, n_valid, tiles, n_live, mask, n_rblk, Q, NQ, n_qblk, xcd, thr, cand_s, cand_i, cand_n, cap, st, gate))
+#define SYMB_E(D_) (aux ? launch_emit_group_fp8<D_, 2>(X, n_valid, tiles, n_live, mask8, qgroup, n_rblk, Q, NQ, n_qblk, xcd, thr, cand_s, cand_i, cand_n, cap, st, gate) \
+                        : launch_emit_group_fp8<D_, 0>(X, n_valid, tiles, n_live, mask8, qgroup, n_rblk, Q, NQ, n_qblk, xcd, thr, cand_s, cand_i, cand_n, cap, st, gate))
   switch (D) {
     case 256: return SYMB_E(256);
     case 384: return SYMB_E(384);

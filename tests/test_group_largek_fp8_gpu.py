@@ -1,0 +1,1076 @@
+"""The grouped emitting e4m3 scan (csrc/hip/index_emit_group_fp8.hip) and the search built on it:
+top-k for 32 < k <= 128 on a GPU fp8 shard under a mask PER QUERY, one scan per chunk of up to
+eight masks instead of one masked emitting search per mask.
+
+Shapes are the project's own smallest that still break such kernels (test_filter_fp8_gpu.py,
+test_fp8_largek_gpu.py, test_filter_group_fp8_gpu.py; restated here, those modules are not
+edited): 64 * 37 + 19 rows (a partial last tile, slices shorter than the ring) and 20 011 rows
+(several workgroups, slices longer than the ring); 1 / 70 / 300 queries (one lane; a ragged
+wave; two query blocks with 44 padding lanes).  A lane holds two queries, i and i + 32, so the
+assignments of queries to groups put those two in different groups at every lane, in the same
+group, and interleaved.  The instances lower the row gate of the route (FP8_LARGE_K_MIN_ROWS = 0)
+as test_fp8_largek_gpu.py does; test 10 runs with nothing lowered.
+
+Tolerances.  Wherever two kernels share Fp8Chain the comparison is bit for bit.  Kernel-level
+sets fixed from the fp32 reference (decoded rows, decoded e4m3 queries) use the gap method and
+the constants of test_fp8_largek_gpu.py: a query's threshold is the midpoint of the largest gap
+between consecutive sorted reference scores, under its OWN mask, among ranks [64, 192), asserted
+to be at least GAP_MIN = max(1e-4, 4 * LIST_SCAN_ERR) first.  LIST_SCAN_ERR = 8.8e-6 is the
+largest |raw / S^2 - fp32 reference| of the masked e4m3 list scan (index_filter_fp8.hip, which
+this change does not touch) measured there over these very shards; test 1 below (same row, same
+score as index_scan_emit_fp8, which that module pins to the list scan) is what lets it carry
+over.  Membership carries no tolerance.  Search-level tolerances are that module's _check_out
+(scores atol 2e-3; recall > 0.99 on random masks only; hard conditions with none)."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from codename_symbiont_amd.ops import reference as R
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+N_SMALL = 64 * 37 + 19
+N_BIG = 20_011
+N_GATE = (1 << 20) + 999
+DIMS = (256, 384, 512, 768, 1024)
+LIST_SCAN_ERR = 8.8e-6      # measured, see the module docstring
+GAP_MIN = max(1e-4, 4 * LIST_SCAN_ERR)
+SENT_N, SENT_I, SENT_S = -7, -9, -12345.0
+# query i -> group, for G groups (test_filter_group_fp8_gpu.py's three)
+ASSIGN = {
+    "interleaved": lambda i, G: (i * 3 + i // 7) % G,
+    "lane pairs apart": lambda i, G: (i // 32) % G,
+    "lane pairs together": lambda i, G: (i // 64) % G,
+}
+
+_shards = {}
+_refs = {}
+
+
+def _shard(D, n):
+    """One random fp8 shard per (width, rows) for the whole module (rows never written after
+    this), with its decoded rows; the small-shard gate of the route is off on it."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    key = (D, n)
+    if key not in _shards:
+        sh = HbmIndexShard(D, n + 100, device=DEV, dtype="fp8")
+        sh.fill_random(n, seed=5 + D + n)
+        sh.FP8_LARGE_K_MIN_ROWS = 0
+        _shards[key] = (sh, sh.unit_rows()[:n])
+    return _shards[key]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _drop_cache():
+    yield
+    _shards.clear()
+    _refs.clear()
+    torch.cuda.empty_cache()
+
+
+def _queries(nq, D, seed=11):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return torch.nn.functional.normalize(torch.randn(nq, D, generator=g), dim=-1).bfloat16().to(DEV)
+
+
+def _quant(q):
+    """(e4m3 bytes the scans take, their decoded values the reference takes)."""
+    from codename_symbiont_amd.ops import kernels as K
+
+    q8 = K.quant_fp8(q)
+    return q8, K.fp8_to_float(q8)
+
+
+def _ref_scores(D, n, nq):
+    """fp32 scores [nq, n] of the module's decoded queries on the shard's decoded rows: computed
+    once per shape, shared, never written."""
+    key = (D, n, nq)
+    if key not in _refs:
+        _refs[key] = _quant(_queries(nq, D))[1] @ _shard(D, n)[1].float().t()
+    return _refs[key]
+
+
+def _tiles_mask(n, tiles):
+    a = torch.zeros(n, dtype=torch.bool)
+    for t in tiles:
+        a[t * 64:(t + 1) * 64] = True
+    return a
+
+
+def _rows_mask(n, idx):
+    return torch.zeros(n, dtype=torch.bool).index_fill_(0, torch.as_tensor(list(idx)), True)
+
+
+def _words(allow):
+    """bool [n] on the host -> packed int64 words on the device."""
+    n = allow.numel()
+    b = np.zeros((n + 63) // 64 * 8, dtype=np.uint8)
+    p = np.packbits(allow.numpy(), bitorder="little")
+    b[:p.size] = p
+    return torch.from_numpy(b).to(DEV).view(torch.int64)
+
+
+def _mask8(allows, slots=None):
+    """bool [n] masks on the host -> int64 [n_words, 8] on the device, mask j in slot slots[j]."""
+    w = [_words(a) for a in allows]
+    m8 = torch.zeros(w[0].numel(), 8, dtype=torch.int64, device=DEV)
+    for j, x in enumerate(w):
+        m8[:, j if slots is None else slots[j]] = x
+    return m8
+
+
+def _union(allows):
+    u = allows[0].clone()
+    for a in allows[1:]:
+        u |= a
+    return u
+
+
+def _kernel_mixes(n):
+    """name -> (bool [n] masks on the host, assignment name): the group mixes of test 2.  Masks
+    with 256 allowed rows or fewer get thr = -inf (every allowed row is the reference set)."""
+    nt = (n + 63) // 64
+    rng = np.random.default_rng(n)
+    ones, zero = torch.ones(n, dtype=torch.bool), torch.zeros(n, dtype=torch.bool)
+    uni = lambda share: torch.from_numpy(rng.random(n) < share)
+    last = list(range((nt - 1) * 64, n))
+    doc = torch.from_numpy(rng.integers(0, 4, n))
+    half = uni(0.5)
+    sub = (torch.arange(n) // 32) % 2 == 0          # every other 32-row sub-tile
+    return {
+        # a group whose queries get nothing next to one that gets every row
+        "ones + zero": ([ones, zero], "lane pairs apart"),
+        "one row": ([_rows_mask(n, [777 % n]), uni(0.5)], "interleaved"),
+        "k-1 rows": ([_rows_mask(n, rng.choice(n, 99, replace=False)), ones], "lane pairs apart"),
+        "one bit per tile": ([_rows_mask(n, [r for r in (t * 64 + (t * 7 + g * 13) % 64
+                                                         for t in range(nt)) if r < n])
+                              for g in range(4)], "interleaved"),
+        "partial last tile only": ([_rows_mask(n, last), _rows_mask(n, last[::2]),
+                                    _rows_mask(n, last[-1:])], "lane pairs apart"),
+        # tiles dead in one group and live in the other, alternately
+        "alternate tiles": ([_tiles_mask(n, range(0, nt, 2)), _tiles_mask(n, range(1, nt, 2))],
+                            "lane pairs apart"),
+        "disjoint documents": ([doc == g for g in range(4)], "interleaved"),
+        "identical masks in two slots": ([half, half.clone(), uni(0.3)], "lane pairs apart"),
+        "eight groups": ([_tiles_mask(n, range(g, nt, 8)) | uni(0.1) for g in range(8)],
+                         "interleaved"),
+        # in every 32-row sub-tile one group's bits are all 0 and the other's all 1: the skip vote
+        # and the all-ones vote meet in one wave (a lane's two queries are in different groups)
+        "sub-tile votes": ([sub, ~sub], "lane pairs apart"),
+        # whole tiles of the union belong only to a group none of a wave's 64 queries is in
+        "tiles foreign to a wave": ([_tiles_mask(n, range(0, nt // 2)),
+                                     _tiles_mask(n, range(nt // 2, nt))], "lane pairs together"),
+    }
+
+
+def _search_mixes(n, k):
+    """name -> (masks, random?): group mixes of the search-level tests."""
+    nt = (n + 63) // 64
+    rng = np.random.default_rng(n + k)
+    ones, zero = torch.ones(n, dtype=torch.bool), torch.zeros(n, dtype=torch.bool)
+    uni = lambda share: torch.from_numpy(rng.random(n) < share)
+    last = list(range((nt - 1) * 64, n))
+    return {
+        "ones next to zero": ([ones, zero], False),
+        "eight documents": ([_tiles_mask(n, range(g, nt, 8)) for g in range(8)], False),
+        "k-1 rows, none, half": ([_rows_mask(n, rng.choice(n, k - 1, replace=False)), zero,
+                                  uni(0.5)], False),
+        "partial last tile only": ([_rows_mask(n, last), _rows_mask(n, last[::2]),
+                                    _rows_mask(n, last[-1:])], False),
+        "uniform 50% x 8": ([uni(0.5) for _ in range(8)], True),
+        "must_not 1% x 5": ([~_tiles_mask(n, range(g, nt, 100)) for g in range(5)], True),
+    }
+
+
+def _close(out, ref, atol, what):
+    err = (out.float() - ref.float()).abs()
+    bad = int((err > atol).sum())
+    assert bad == 0, f"{what}: {bad} elems off, max err {float(err.max()):.4g}"
+
+
+def _same(sh, q, s, r, s1, r1, what):
+    """test_fp8_largek_gpu.py's rule for two searches that must agree: scores bit for bit; rows
+    equal except inside runs of equal scores (the emitting scans hand their slots out by
+    atomics).  A run can go on past k, so a LAST slot whose rows differ without an equal
+    neighbour must be proved a tie: the two rows, searched alone under a two-row mask (k = 2: the
+    list scan, the same per-row MFMA chain), score the same bit for bit, the slot's score."""
+    assert torch.equal(s, s1), f"{what}: scores differ"
+    rr, gg = r.long(), r1.long()
+    tie = torch.zeros_like(rr, dtype=torch.bool)
+    tie[:, 1:] |= s[:, 1:] == s[:, :-1]
+    tie[:, :-1] |= s[:, :-1] == s[:, 1:]
+    diff = (rr != gg) & ~tie
+    assert not bool(diff[:, :-1].any()), f"{what}: rows differ outside ties"
+    for i in torch.nonzero(diff[:, -1]).flatten().tolist():
+        a, b = int(rr[i, -1]), int(gg[i, -1])
+        assert a >= 0 and b >= 0, f"{what}: query {i}, last slot {a} against {b}"
+        assert b not in rr[i].tolist() and a not in gg[i].tolist(), f"{what}: query {i}"
+        s2, r2 = sh.search(q[i:i + 1], 2, allow=[a, b])
+        assert sorted(r2[0].tolist()) == sorted((a, b)), f"{what}: query {i}"
+        assert float(s2[0, 0]) == float(s2[0, 1]) == float(s[i, -1]), \
+            f"{what}: query {i}: last slot {a} against {b} is no tie"
+
+
+def _check_out(s, r, rows, qd, k, allows_d, group_of, what, random_mask=False):
+    """(scores, rows) of one grouped search against the reference over the decoded rows [n, D] and
+    decoded queries: test_fp8_largek_gpu.py::_check_out with the mask a per-query one."""
+    n, nq = rows.shape[0], qd.shape[0]
+    ref_s, ref_i = R.grouped_filtered_topk_ref(rows, qd, k, allows_d, group_of)
+    torch.cuda.synchronize()
+    assert s.shape == (nq, k) and r.shape == (nq, k), what
+    assert s.dtype == torch.float32 and r.dtype == torch.int32, what
+    fin = torch.isfinite(ref_s)
+    g_d = torch.tensor(group_of, device=DEV)
+    n_allowed = torch.stack(allows_d).sum(1)[g_d]
+    assert torch.equal(fin.sum(1), n_allowed.clamp_max(k)), what
+    # the (-inf, -1) tail is exactly where the reference has it
+    assert torch.equal(torch.isfinite(s), fin), what
+    assert bool((s[~fin] == -math.inf).all()) and bool((r[~fin] == -1).all()), what
+    rr = r.long()
+    # hard conditions: rows the query's OWN mask allows, none at or past `visible`, none twice
+    assert bool((rr[fin] >= 0).all()) and bool((rr[fin] < n).all()), what
+    own = torch.stack(allows_d)[g_d[:, None].expand_as(rr), rr.clamp_min(0)]
+    assert bool(own[fin].all()), f"{what}: a row another query's mask allows came back"
+    srt = torch.sort(torch.where(fin, rr, torch.arange(-k, 0, device=DEV).expand_as(rr)), 1).values
+    assert bool((srt[:, 1:] != srt[:, :-1]).all()), f"{what}: a row came back twice"
+    _close(s[fin], ref_s[fin], 2e-3, f"{what}: scores")
+    true = R.row_scores_ref(rows, qd, rr.clamp_min(0))
+    _close(s[fin], true[fin], 2e-3, f"{what}: returned rows' true scores")
+    # a mask with k rows or fewer: exactly its rows
+    for i in torch.nonzero(n_allowed <= k).flatten().tolist():
+        m = int(n_allowed[i])
+        want = torch.nonzero(allows_d[group_of[i]]).flatten()
+        assert torch.equal(torch.sort(rr[i, :m]).values, want), f"{what}: not the allowed set"
+    if random_mask:
+        hit = ((rr[:, :, None] == ref_i[:, None, :]) & fin[:, :, None]).any(-1).sum()
+        assert float(hit) / float(fin.sum()) > 0.99, what
+
+
+def _gap_threshold(masked_sc, lo, hi, what):
+    """Per query: the midpoint of the largest gap between consecutive sorted scores among ranks
+    [lo, hi) of ``masked_sc`` [nq, n] (-inf = disallowed), in raw units; the gap is asserted
+    first (test_fp8_largek_gpu.py)."""
+    from codename_symbiont_amd.ops.kernels import FP8_SCALE
+
+    top = torch.topk(masked_sc, hi, dim=1).values
+    assert bool(torch.isfinite(top).all()), what
+    gaps = top[:, lo:hi - 1] - top[:, lo + 1:hi]
+    g, j = gaps.max(1)
+    assert float(g.min()) >= GAP_MIN, f"{what}: reference gap {float(g.min()):.3g} below {GAP_MIN}"
+    a = torch.gather(top, 1, (lo + j)[:, None])[:, 0]
+    b = torch.gather(top, 1, (lo + j + 1)[:, None])[:, 0]
+    return ((a + b) * 0.5 * (FP8_SCALE * FP8_SCALE)).contiguous()
+
+
+def _own(allows, group_of):
+    """bool [nq, n] on the device: the rows each query's own mask allows."""
+    return torch.stack([a.to(DEV) for a in allows])[torch.tensor(group_of, device=DEV)]
+
+
+def _thr_for(allows, group_of, sc, what):
+    """Per query, under its own mask: the gap threshold, or -inf for a mask with too few allowed
+    rows to have ranks [64, 192)."""
+    nq = sc.shape[0]
+    thr = torch.full((nq,), -math.inf, device=DEV)
+    for g, a in enumerate(allows):
+        idx = torch.tensor([i for i in range(nq) if group_of[i] == g], dtype=torch.long, device=DEV)
+        if idx.numel() == 0 or int(a.sum()) <= 256:
+            continue
+        msc = torch.where(a.to(DEV)[None, :], sc[idx], torch.full_like(sc[idx], -math.inf))
+        thr[idx] = _gap_threshold(msc, 64, 192, f"{what}: group {g}")
+    return thr
+
+
+def _bufs(nq, cap):
+    """cand_s, cand_i [nq * cap + 64] and cand_n [nq + 64], each ending in a 64-entry sentinel
+    guard."""
+    return (torch.full((nq * cap + 64,), SENT_S, device=DEV),
+            torch.full((nq * cap + 64,), SENT_I, dtype=torch.int32, device=DEV),
+            torch.full((nq + 64,), SENT_N, dtype=torch.int32, device=DEV))
+
+
+def _emit_group(sh, n, mask8, qgroup, tiles, n_live, q8, thr, cap, n_rblk, gate=None, bufs=None,
+                zero_cnt=True):
+    """index_scan_emit_group_fp8 through the wrapper -> the guarded buffers."""
+    from codename_symbiont_amd.ops import kernels as K
+
+    nq = q8.shape[0]
+    cs, ci, cn = bufs if bufs is not None else _bufs(nq, cap)
+    K.index_scan_emit_group_fp8(sh.rows, n, mask8, qgroup, tiles, n_live, q8, thr, cs[:nq * cap],
+                                ci[:nq * cap], cn[:nq], cap, n_rblk, 1, gate, zero_cnt)
+    torch.cuda.synchronize()
+    return cs, ci, cn
+
+
+def _group_inputs(allows, group_of, n, slots=None):
+    """mask8, qgroup, tiles, n_live of bool masks on the host (filter_tiles of their union)."""
+    from codename_symbiont_amd.ops import kernels as K
+
+    mask8 = _mask8(allows, slots)
+    tiles, n_live = K.filter_tiles(_words(_union(allows)), n)
+    qgroup = torch.tensor([g if slots is None else slots[g] for g in group_of], dtype=torch.int32,
+                          device=DEV)
+    return mask8, qgroup, tiles, n_live
+
+
+def _emit_single(sh, n, allow, q8, thr, cap, n_rblk):
+    """index_scan_emit_fp8 of all queries under one mask -> (cand_s, cand_i [nq, cap], cand_n)."""
+    from codename_symbiont_amd.ops import kernels as K
+
+    nq = q8.shape[0]
+    mask = sh.make_mask(allow.to(DEV))
+    cs = torch.full((nq, cap), SENT_S, device=DEV)
+    ci = torch.full((nq, cap), SENT_I, dtype=torch.int32, device=DEV)
+    cn = torch.zeros(nq, dtype=torch.int32, device=DEV)
+    K.index_scan_emit_fp8(sh.rows, n, mask.words, mask.tiles, mask.n_live, q8, thr, cs, ci, cn,
+                          cap, n_rblk, 1)
+    torch.cuda.synchronize()
+    return cs, ci, cn
+
+
+def _emitted_matrix(ci, cn, nq, n, cap, what):
+    """bool [nq, n]: row emitted for the query, and the valid-slot matrix [nq, cap]; asserts ids
+    in range (below ``visible``) and no row twice."""
+    cnt = cn[:nq].long()
+    assert int(cnt.min()) >= 0 and int(cnt.max()) <= cap, f"{what}: cand_n outside [0, cap]"
+    valid = torch.arange(cap, device=DEV)[None, :] < cnt[:, None]
+    ids = ci[:nq * cap].view(nq, cap).long()
+    assert bool(((ids >= 0) & (ids < n))[valid].all()), f"{what}: a row id outside [0, n_valid)"
+    times = torch.zeros(nq, n, dtype=torch.int32, device=DEV)
+    times.scatter_add_(1, ids.clamp(0, n - 1), valid.to(torch.int32))
+    assert int(times.max()) <= 1, f"{what}: a row was emitted twice"
+    return times > 0, valid
+
+
+def _dense(cs, ci, valid, nq, n, cap):
+    """float [nq, n]: the emitted raw score of each (query, row), -inf where none."""
+    ids = ci[:nq * cap].view(nq, cap).long().clamp(0, n - 1)
+    sc = torch.where(valid, cs[:nq * cap].view(nq, cap), torch.full((), -math.inf, device=DEV))
+    out = torch.full((nq, n + 1), -math.inf, device=DEV)
+    # (invalid slots land in the spare column)
+    out.scatter_(1, torch.where(valid, ids, torch.full_like(ids, n)), sc)
+    return out[:, :n]
+
+
+def _check_emitted(sh, n, allows, group_of, q8, sc, thr, n_rblk, what, inputs=None):
+    """One launch against the reference set {rows the query's own mask allows whose reference
+    score lies above thr}: counts, sentinels, membership without tolerance, scores within half
+    the gap."""
+    from codename_symbiont_amd.ops.kernels import FP8_SCALE
+
+    nq = q8.shape[0]
+    own = _own(allows, group_of)
+    msc = torch.where(own, sc, torch.full_like(sc, -math.inf))
+    want = msc * (FP8_SCALE * FP8_SCALE) > thr[:, None]
+    cap = max(512, int(want.sum(1).max()))
+    mask8, qgroup, tiles, n_live = inputs or _group_inputs(allows, group_of, n)
+    cs, ci, cn = _emit_group(sh, n, mask8, qgroup, tiles, n_live, q8, thr, cap, n_rblk)
+    assert torch.equal(cn[:nq].long(), want.sum(1)), f"{what}: cand_n"
+    # queries past NQ in the padded block emitted nothing; nothing past the buffers' ends
+    assert bool((cn[nq:] == SENT_N).all()), f"{what}: counters past NQ written"
+    assert bool((cs[nq * cap:] == SENT_S).all()) and bool((ci[nq * cap:] == SENT_I).all()), what
+    got, valid = _emitted_matrix(ci, cn, nq, n, cap, what)
+    assert not bool((got & ~own).any()), f"{what}: a row the query's mask disallows"
+    assert torch.equal(got, want), f"{what}: not the reference set"
+    ids = ci[:nq * cap].view(nq, cap).long()
+    true = torch.gather(sc, 1, ids.clamp(0, n - 1))
+    raw = cs[:nq * cap].view(nq, cap) * (1.0 / (FP8_SCALE * FP8_SCALE))
+    # (half the gap: the clearance the thresholds above rely on)
+    _close(raw[valid], true[valid], GAP_MIN / 2, f"{what}: emitted scores")
+    assert bool((cs[:nq * cap].view(nq, cap)[~valid] == SENT_S).all()), what
+    assert bool((ci[:nq * cap].view(nq, cap)[~valid] == SENT_I).all()), what
+
+
+def _bar(monkeypatch, *names):
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    for name in names:
+        def barred(self, *a, _name=name, **kw):
+            raise AssertionError(f"the search took {_name}")
+        monkeypatch.setattr(HbmIndexShard, name, barred)
+
+
+def _count(monkeypatch):
+    """-> dict of lists collecting the calls of the new chunk method, the grouped seed wrapper
+    (its kmax and stride), the new kernel wrapper (its queries) and _search_masked."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+    from codename_symbiont_amd.ops import kernels as K
+
+    calls = {"chunk": [], "seed": [], "emit": [], "masked": []}
+    real_c, real_m = HbmIndexShard._search_group_chunk_large_k, HbmIndexShard._search_masked
+    real_s, real_e = K.index_scan_filter_group_fp8, K.index_scan_emit_group_fp8
+
+    def chunk(self, q8, *a, **kw):
+        calls["chunk"].append(q8.shape[0])
+        return real_c(self, q8, *a, **kw)
+
+    def masked(self, q, *a, **kw):
+        calls["masked"].append(q.shape[0])
+        return real_m(self, q, *a, **kw)
+
+    def seed(*a, **kw):
+        calls["seed"].append((a[7], a[12]))             # (kmax, stride)
+        return real_s(*a, **kw)
+
+    def emit(*a, **kw):
+        calls["emit"].append(a[6].shape[0])
+        return real_e(*a, **kw)
+
+    monkeypatch.setattr(HbmIndexShard, "_search_group_chunk_large_k", chunk)
+    monkeypatch.setattr(HbmIndexShard, "_search_masked", masked)
+    monkeypatch.setattr(K, "index_scan_filter_group_fp8", seed)
+    monkeypatch.setattr(K, "index_scan_emit_group_fp8", emit)
+    return calls
+
+
+# 1 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", DIMS)
+def test_same_row_same_score(D):
+    """thr = -inf and a cap that holds every row: each query's emitted (row, raw score) set is,
+    bit for bit, what index_scan_emit_fp8 emits for it under its own group's mask -- no row
+    twice, none at or past n_valid, none disallowed -- at both shard sizes under the three
+    assignments of queries to groups."""
+    nq = 70
+    q8, _ = _quant(_queries(nq, D, seed=21))
+    thr = torch.full((nq,), -math.inf, device=DEV)
+    for n, n_rblk in ((N_SMALL, 3), (N_BIG, 7)):
+        sh, _ = _shard(D, n)
+        nt = (n + 63) // 64
+        rng = np.random.default_rng(n + D)
+        allows = [torch.from_numpy(rng.random(n) < 0.5), torch.ones(n, dtype=torch.bool),
+                  _tiles_mask(n, range(0, nt, 2)) & torch.from_numpy(rng.random(n) < 0.7)]
+        cap = n
+        single = []
+        for a in allows:
+            cs, ci, cn = _emit_single(sh, n, a, q8, thr, cap, n_rblk)
+            assert bool((cn == int(a.sum())).all())
+            _, valid = _emitted_matrix(ci.flatten(), cn, nq, n, cap, f"D={D} n={n} single")
+            single.append(_dense(cs.flatten(), ci.flatten(), valid, nq, n, cap))
+        for aname, f in ASSIGN.items():
+            what = f"D={D} n={n} {aname}"
+            group_of = [f(i, 3) for i in range(nq)]
+            own = _own(allows, group_of)
+            cs, ci, cn = _emit_group(sh, n, *_group_inputs(allows, group_of, n), q8, thr, cap, n_rblk)
+            assert torch.equal(cn[:nq].long(), own.sum(1)), f"{what}: cand_n"
+            assert bool((cn[nq:] == SENT_N).all()), f"{what}: counters past NQ written"
+            assert bool((cs[nq * cap:] == SENT_S).all()) and bool((ci[nq * cap:] == SENT_I).all())
+            got, valid = _emitted_matrix(ci, cn, nq, n, cap, what)
+            assert torch.equal(got, own), f"{what}: not the query's own allowed rows, each once"
+            want = torch.stack(single)[torch.tensor(group_of, device=DEV), torch.arange(nq, device=DEV)]
+            assert torch.equal(_dense(cs, ci, valid, nq, n, cap), want), \
+                f"{what}: a row scores differently in the two kernels"
+
+
+# 2 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D,nq", [(D, nq) for D in DIMS for nq in (1, 70, 300)])
+def test_emitted_set_is_the_reference_set(D, nq):
+    q8, _ = _quant(_queries(nq, D))
+    for n, n_rblk in ((N_SMALL, 5), (N_BIG, 7)):
+        sh, _ = _shard(D, n)
+        sc = _ref_scores(D, n, nq)
+        for name, (allows, aname) in _kernel_mixes(n).items():
+            what = f"D={D} nq={nq} n={n} {name}"
+            group_of = [ASSIGN[aname](i, len(allows)) for i in range(nq)]
+            _check_emitted(sh, n, allows, group_of, q8, sc, _thr_for(allows, group_of, sc, what),
+                           n_rblk, what)
+
+
+# 3 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", DIMS)
+def test_slices_around_the_ring_depth(D):
+    """Unions of NS - 1 ... 2 NS + 1 live tiles spread over the shard and split over two or three
+    groups, walked by one workgroup, by three, and by more row slots than there are live tiles
+    (empty slices): slices shorter than the ring, as long as it and longer -- the prologue's NS
+    list reads, the clamped re-loads and the tail prefetches.  At 768 a list entry is two
+    intervals."""
+    from codename_symbiont_amd.ops._ext import hip
+
+    n, nq = N_SMALL, 70
+    nt = (n + 63) // 64
+    sh, _ = _shard(D, n)
+    q8, _ = _quant(_queries(nq, D))
+    sc = _ref_scores(D, n, nq)
+    rng = np.random.default_rng(D)
+    ns = hip().filter_fp8_ring_depth(D)
+    assert 2 <= ns <= 8
+    group_of3 = lambda G: [(i // 32) % G for i in range(nq)]
+    for m in range(max(1, ns - 1), 2 * ns + 2):
+        live = sorted({int(round(t)) for t in np.linspace(0, nt - 1, m)})
+        assert len(live) == m
+        G = 2 + m % 2
+        allows = [torch.zeros(n, dtype=torch.bool) for _ in range(G)]
+        for j, t in enumerate(live):
+            # tile j belongs to group j % G (a random half of it, never empty); every third tile
+            # also to the next group
+            lo, hi = t * 64, min(n, t * 64 + 64)
+            for g in {j % G, (j + 1) % G if j % 3 == 0 else j % G}:
+                allows[g][lo:hi] = torch.from_numpy(rng.random(hi - lo) < 0.5)
+                allows[g][lo] = True
+        group_of = group_of3(G)
+        inputs = _group_inputs(allows, group_of, n)
+        assert int(inputs[3]) == m
+        thr = torch.full((nq,), -math.inf, device=DEV)      # (at most 2 NS + 1 tiles: few rows)
+        for n_rblk in (1, 3, m + 2):
+            _check_emitted(sh, n, allows, group_of, q8, sc, thr, n_rblk,
+                           f"D={D} live={m} n_rblk={n_rblk}", inputs)
+
+
+# 4 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D,nq", [(256, 70), (768, 130), (1024, 20)])
+def test_overflow_append_and_gate(D, nq):
+    """cap = 64 under thr = -inf: every query of a non-empty group overflows.  A slot written at
+    or past cap would land in the next query's slots or in the guard, so every slot below cap
+    must hold a row of the query's own mask with the score THIS query gives it (from a launch
+    whose cap holds every row); the select raises its flag.  zero_cnt = False appends.  A closed
+    gate leaves every buffer, counters included, as it was."""
+    from codename_symbiont_amd.ops._ext import hip, stream_handle
+
+    n, cap, big, n_rblk = N_SMALL, 64, N_SMALL, 5
+    sh, _ = _shard(D, n)
+    q8, _ = _quant(_queries(nq, D, seed=31))
+    thr = torch.full((nq,), -math.inf, device=DEV)
+    rng = np.random.default_rng(D)
+    allows = [torch.ones(n, dtype=torch.bool), torch.from_numpy(rng.random(n) < 0.5),
+              torch.from_numpy(rng.random(n) < 0.2)]
+    group_of = [(i // 32 + i) % 3 for i in range(nq)]
+    own = _own(allows, group_of)
+    n_own = own.sum(1)
+    inputs = _group_inputs(allows, group_of, n)
+    fs, fi, fn = _emit_group(sh, n, *inputs, q8, thr, big, n_rblk)
+    _, fvalid = _emitted_matrix(fi, fn, nq, n, big, f"D={D}")
+    dense = _dense(fs, fi, fvalid, nq, n, big)
+    # a closed gate: untouched, sentinels and all
+    shut = torch.zeros(1, dtype=torch.int32, device=DEV)
+    cs, ci, cn = _emit_group(sh, n, *inputs, q8, thr, cap, n_rblk, gate=shut)
+    assert bool((cn == SENT_N).all()) and bool((cs == SENT_S).all()) and bool((ci == SENT_I).all())
+    bufs = _emit_group(sh, n, *inputs, q8, thr, cap, n_rblk, gate=shut + 1, bufs=(cs, ci, cn))
+    for rep in (1, 2):
+        what = f"D={D} nq={nq} pass {rep}"
+        if rep == 2:                                     # zero_cnt = False appends
+            bufs = _emit_group(sh, n, *inputs, q8, thr, cap, n_rblk, bufs=bufs, zero_cnt=False)
+        cs, ci, cn = bufs
+        assert torch.equal(cn[:nq].long(), rep * n_own), f"{what}: cand_n is not the count"
+        assert int(cn[:nq].min()) > cap
+        assert bool((cn[nq:] == SENT_N).all()), f"{what}: counters past NQ written"
+        assert bool((cs[nq * cap:] == SENT_S).all()) and bool((ci[nq * cap:] == SENT_I).all()), \
+            f"{what}: written past the buffers"
+        ids = ci[:nq * cap].view(nq, cap).long()
+        assert bool(((ids >= 0) & (ids < n)).all()), what
+        assert bool(torch.gather(own, 1, ids).all()), f"{what}: a slot holds a disallowed row"
+        srt = torch.sort(ids, 1).values
+        assert bool((srt[:, 1:] != srt[:, :-1]).all()), f"{what}: a row twice"
+        assert torch.equal(cs[:nq * cap].view(nq, cap), torch.gather(dense, 1, ids)), \
+            f"{what}: a slot holds another query's score"
+    # the select sees counts past the cap and raises the flag
+    k = 40
+    out_s = torch.empty(nq, k, device=DEV)
+    out_i = torch.empty(nq, k, dtype=torch.int32, device=DEV)
+    ovf = torch.zeros(1, dtype=torch.int32, device=DEV)
+    cnt = cn[:nq].contiguous()
+    hip().topk_select_counted(cs.data_ptr(), ci.data_ptr(), cnt.data_ptr(), cap, nq, 128, k,
+                              out_s.data_ptr(), out_i.data_ptr(), ovf.data_ptr(),
+                              stream_handle(sh.device), gate=0, reset_ovf=False)
+    torch.cuda.synchronize()
+    assert int(ovf) == 1
+
+
+# 5 ------------------------------------------------------------------------------------------------
+def test_raw_wrapper_on_dirty_input():
+    """The kernel on words whose bits at and past `visible` are set (in the last tile and in words
+    past it), with e4m3 copies of the queries in the slab's rows past `visible` (a scan that
+    ignored n_valid would emit them at ~1.0), qgroup entries of 8 + g, garbage in the unused
+    slots and the tile list filled past n_live (with an in-range tile, so nothing can fault)."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+    from codename_symbiont_amd.ops import kernels as K
+
+    D, n, nq, n_rblk = 384, N_SMALL, 70, 5
+    sh = HbmIndexShard(D, n + 200, device=DEV, dtype="fp8")
+    sh.fill_random(n, seed=3)
+    q = _queries(nq, D)
+    q8, qd = _quant(q)
+    sc = qd @ sh.unit_rows()[:n].float().t()
+    sh.rows[n:n + nq].copy_(q8)                     # unpublished rows of the last tile and beyond
+    rng = np.random.default_rng(4)
+    slots = (0, 2, 7)
+    allows = [torch.from_numpy(rng.random(n) < share) for share in (0.6, 0.5, 0.3)]
+    group_of = [(i // 32 + i) % 3 for i in range(nq)]
+    nw = (n + 63) // 64
+    mask8 = torch.zeros(nw + 2, 8, dtype=torch.int64, device=DEV)
+    mask8[:nw] = _mask8(allows, slots)
+    for g in slots:                                 # dirty: every bit at and past n, words past it
+        mask8[n // 64, g] |= -1 << (n % 64)
+        mask8[nw:, g] = -1
+    union = (mask8[:nw, 0] | mask8[:nw, 2] | mask8[:nw, 7]).contiguous()
+    tiles, n_live = K.filter_tiles(union, n)
+    tiles[int(n_live):] = 3                         # past n_live: in range, but not the list's
+    for g in range(8):                              # slots no query names: garbage
+        if g not in slots:
+            mask8[:, g] = torch.from_numpy(rng.integers(-2**62, 2**62, nw + 2)).to(DEV)
+    # every other query names its slot as 8 + slot: only the low three bits count
+    qgroup = torch.tensor([slots[g] + (8 if i % 2 else 0) for i, g in enumerate(group_of)],
+                          dtype=torch.int32, device=DEV)
+    what = "dirty input"
+    _check_emitted(sh, n, allows, group_of, q8, sc, _thr_for(allows, group_of, sc, what), n_rblk,
+                   what, (mask8, qgroup, tiles, n_live))
+    thr = torch.full((nq,), -math.inf, device=DEV)
+    _check_emitted(sh, n, allows, group_of, q8, sc, thr, n_rblk, what + ", thr -inf",
+                   (mask8, qgroup, tiles, n_live))
+
+
+# 6 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D,k,nq", [(D, k, nq) for D in (384, 1024)
+                                    for k, nq in ((33, 70), (100, 300), (128, 130))])
+def test_search_takes_the_grouped_emitting_scan(D, k, nq, monkeypatch):
+    """sh.search(q, k, allow=MaskGroups) at 32 < k <= 128 with the single-mask search and the
+    matmul barred: one chunk is one call of the chunk method, one seed pass (two where the
+    coarse pass runs) and one emitting scan.  (On the parent commit only the per-mask loop
+    serves this search, and the bar fails it.)  Results against the reference and, per group,
+    against the single-mask search by _same."""
+    q = _queries(nq, D)
+    _, qd = _quant(q)
+    for n in (N_SMALL, N_BIG):
+        sh, rows = _shard(D, n)
+        for name, (allows, rnd) in _search_mixes(n, k).items():
+            G = len(allows)
+            what = f"D={D} n={n} k={k} nq={nq} {name}"
+            allows_d = [a.to(DEV) for a in allows]
+            # (alternating: a lane's two queries apart / interleaved, which names all eight groups)
+            group_of = [ASSIGN["lane pairs apart" if G <= nq // 32 else "interleaved"](i, G)
+                        for i in range(nq)]
+            mg = sh.make_mask_groups(allows_d, group_of)
+            assert len(mg) == G and sh._group_large_k_serves(k, mg)
+            for coarse in (False, True):
+                with monkeypatch.context() as m:
+                    calls = _count(m)
+                    _bar(m, "_search_masked", "_search_matmul")
+                    if coarse:                          # the seed pass's own seed, on this instance
+                        sh.SEED_MIN_ROWS = 0
+                    try:
+                        s, r = sh.search(q, k, allow=mg)
+                    finally:
+                        sh.__dict__.pop("SEED_MIN_ROWS", None)
+                    stride = sh.FILTER_LARGE_K_STRIDE
+                    assert calls["chunk"] == [nq] and calls["emit"] == [nq], what
+                    assert calls["seed"] == ([(16, stride * sh.FILTER_LARGE_K_COARSE)] * coarse
+                                             + [(32, stride)]), what
+                assert int(sh._filter_large_k_last[1]) == 0, what
+                if coarse:
+                    _same(sh, q, s, r, s0, r0, f"{what}: coarse pass on against off")
+                s0, r0 = s, r
+            assert "SEED_MIN_ROWS" not in sh.__dict__
+            _check_out(s, r, rows, qd, k, allows_d, group_of, what, rnd)
+            for g, a in enumerate(allows_d):
+                idx = [i for i in range(nq) if group_of[i] == g]
+                if idx:
+                    sg, rg = sh._search_masked(q[idx], k, None, a)
+                    _same(sh, q[idx], s[idx], r[idx], sg, rg, f"{what}: group {g}")
+
+
+@pytest.mark.parametrize("D", [384, 1024])
+def test_seed_on_equals_seed_off(D):
+    """T from the seed pass against T = -inf, where the cap holds every row."""
+    from codename_symbiont_amd.ops import kernels as K
+
+    k, nq, n = 100, 130, N_SMALL
+    sh, _ = _shard(D, n)
+    q = _queries(nq, D, seed=41)
+    q8 = K.quant_fp8(q)
+    assert sh.LARGE_K_CAP >= n
+    for name, (allows, _) in _search_mixes(n, k).items():
+        mg = sh.make_mask_groups([a.to(DEV) for a in allows],
+                                 [(i * 3 + i // 7) % len(allows) for i in range(nq)])
+        ch = mg.chunk(0)
+        assert ch["idx"].tolist() == list(range(nq))
+        s1, r1 = sh._search_group_chunk_large_k(q8, k, mg, ch, None, seed=True)
+        s0, r0 = sh._search_group_chunk_large_k(q8, k, mg, ch, None, seed=False)
+        torch.cuda.synchronize()
+        _same(sh, q, s1, r1, s0, r0, f"D={D} {name}")
+
+
+@pytest.mark.parametrize("G,chunks", [(9, 2), (17, 3)])
+def test_chunks_of_eight_masks(G, chunks, monkeypatch):
+    D, n, k, nq = 384, N_SMALL, 100, 60
+    sh, rows = _shard(D, n)
+    q = _queries(nq, D, seed=51)
+    _, qd = _quant(q)
+    rng = np.random.default_rng(G)
+    allows = [torch.from_numpy(rng.random(n) < 0.3) for _ in range(G)]
+    allows_d = [a.to(DEV) for a in allows]
+    group_of = [(i * 5) % G for i in range(nq)]
+    mg = sh.make_mask_groups(allows_d, group_of)
+    assert mg.n_chunks == chunks
+    with monkeypatch.context() as m:
+        calls = _count(m)
+        _bar(m, "_search_masked", "_search_matmul")
+        s, r = sh.search(q, k, allow=mg)
+    assert len(calls["chunk"]) == len(calls["emit"]) == chunks and sum(calls["chunk"]) == nq
+    assert len(calls["seed"]) == chunks
+    _check_out(s, r, rows, qd, k, allows_d, group_of, f"{G} masks", True)
+
+
+def test_one_mask_and_k_32_keep_their_routes(monkeypatch):
+    """One distinct mask (given once, or twice as equal masks) goes to _search_masked and the new
+    chunk method never runs; k = 32 still takes the list-scan chunk."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    D, n, nq = 384, N_BIG, 70
+    sh, rows = _shard(D, n)
+    q = _queries(nq, D, seed=52)
+    _, qd = _quant(q)
+    rng = np.random.default_rng(53)
+    a = torch.from_numpy(rng.random(n) < 0.2).to(DEV)
+    s0, r0 = sh.search(q, 100, allow=a)
+    with monkeypatch.context() as m:
+        calls = _count(m)
+        for masks, group_of in (([a], [0] * nq), ([a, a.clone()], [i % 2 for i in range(nq)])):
+            mg = sh.make_mask_groups(masks, group_of)
+            assert len(mg) == 1 and not sh._group_large_k_serves(100, mg)
+            s, r = sh.search(q, 100, allow=mg)
+            _same(sh, q, s, r, s0, r0, "one mask")
+        assert calls["chunk"] == [] and calls["emit"] == [] and calls["masked"] == [nq, nq]
+    allows_d = [a, torch.from_numpy(rng.random(n) < 0.4).to(DEV)]
+    group_of = [(i // 32) % 2 for i in range(nq)]
+    mg = sh.make_mask_groups(allows_d, group_of)
+    took = []
+    real = HbmIndexShard._search_group_chunk
+    with monkeypatch.context() as m:
+        calls = _count(m)
+        _bar(m, "_search_masked", "_search_matmul")
+        m.setattr(HbmIndexShard, "_search_group_chunk",
+                  lambda self, *a, **kw: (took.append(1), real(self, *a, **kw))[1])
+        s, r = sh.search(q, 32, allow=mg)
+        assert took == [1] and calls["chunk"] == [] and calls["emit"] == []
+        assert not sh._group_large_k_serves(32, mg) and sh._group_scan_serves(32, mg)
+    _check_out(s, r, rows, qd, 32, allows_d, group_of, "k = 32", True)
+
+
+# 7 ------------------------------------------------------------------------------------------------
+def test_overflow_falls_back_on_the_per_mask_loop(monkeypatch):
+    """LARGE_K_CAP = 64 on the instance: the chunk overflows, the per-mask loop answers (its own
+    searches overflow too and end in the matmul), and the results equal those of each group's
+    single-mask search on the same instance."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    D, n, k, nq = 384, N_BIG, 100, 40
+    sh = HbmIndexShard(D, n + 100, device=DEV, dtype="fp8")
+    sh.fill_random(n, seed=61)
+    sh.FP8_LARGE_K_MIN_ROWS, sh.LARGE_K_CAP = 0, 64
+    q = _queries(nq, D, seed=62)
+    _, qd = _quant(q)
+    rows = sh.unit_rows()[:n]
+    rng = np.random.default_rng(7)
+    allows = [torch.from_numpy(rng.random(n) < share) for share in (0.3, 0.5, 0.1)]
+    allows_d = [a.to(DEV) for a in allows]
+    group_of = [(i // 32 + i) % 3 for i in range(nq)]
+    mg = sh.make_mask_groups(allows_d, group_of)
+    with monkeypatch.context() as m:
+        calls = _count(m)
+        s, r = sh.search(q, k, allow=mg)
+    assert calls["chunk"] == [nq] and calls["emit"] == [nq]
+    assert sorted(calls["masked"]) == sorted(group_of.count(g) for g in range(3))
+    _check_out(s, r, rows, qd, k, allows_d, group_of, "overflow", True)
+    for g, a in enumerate(allows_d):
+        idx = [i for i in range(nq) if group_of[i] == g]
+        sg, rg = sh.search(q[idx], k, allow=a)
+        _same(sh, q[idx], s[idx], r[idx], sg, rg, f"overflow: group {g}")
+    # and the chunk method itself reports the overflow
+    q8 = _quant(q)[0]
+    assert sh._search_group_chunk_large_k(q8, k, mg, mg.chunk(0), None) is None
+    cnt, ovf = sh._filter_large_k_last
+    assert int(ovf) == 1 and int(cnt.max()) > 64
+
+
+# 8 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D,family", [(D, f) for D in (384, 1024)
+                                      for f in ("dups", "ternary", "orthant")])
+def test_lattice_grouped_large_k_is_bit_exact(D, family, monkeypatch):
+    """tests/lattice.py data (every dot product exact in fp32 under any summation order): three
+    masks over 48 queries at k = 64, each query exact under its own mask bit for bit, ties across
+    the k-th place and across the masks included, in the style of
+    test_lattice_gpu.py::test_grouped_scan_is_bit_exact."""
+    import lattice as L
+    from codename_symbiont_amd.index.shard import TILE_ROWS, HbmIndexShard
+
+    n, nq, k = N_BIG, 48, 64
+    plan = {}
+    if family == "orthant":
+        x = L.orthant(n, D, seed=n + D + 1, device=DEV)
+        q = L.orthant_queries(nq, D, seed=n + D + 2, device=DEV)
+    else:
+        gen = L.ternary if family == "ternary" else L.dense
+        x = gen(n, D, seed=n + D + 3, device=DEV)
+        q = gen(nq, D, seed=n + D + 4, device=DEV)
+        q[-4:] = x[torch.tensor([5, n // 3, n // 2, n - 2], device=DEV)]
+        if family == "dups":
+            # 2, 9 and 70 exact copies of the best rows of queries 0, 1 and 2: 70 > k ties across
+            # the k-th place
+            best = L.oracle_topk(x, q[:3], 1)[1][:, 0].tolist()
+            x, plan = L.with_duplicates(x, best, [2, 9, 70], seed=n + D)
+
+    def allowed(seed, plan=None):
+        """About half the rows, two whole tiles dead, the last visible row allowed; with a plan,
+        the first source allowed and one of its copies masked out (a tie across the mask)."""
+        a = torch.rand(n, generator=torch.Generator(device=DEV).manual_seed(seed), device=DEV) < 0.5
+        a[2 * TILE_ROWS:3 * TILE_ROWS] = False
+        a[(n // TILE_ROWS - 1) * TILE_ROWS:(n // TILE_ROWS) * TILE_ROWS] = False
+        a[n - 1] = True
+        if plan:
+            src = next(iter(plan))
+            twin = [p for p in plan[src] if p != n - 1][0]
+            a[src], a[twin] = True, False
+        return a
+
+    sh = HbmIndexShard(D, n + TILE_ROWS, device=DEV, dtype="fp8")
+    sh.append_unit(x)
+    sh.SEED_MIN_ROWS = sh.FP8_LARGE_K_MIN_ROWS = 0
+    assert torch.equal(sh.unit_rows()[:n], x), "the e4m3 image is lossless on lattice data"
+    allows = [allowed(7, plan), allowed(8), allowed(9, plan)]
+    group_of = [(i * 7) % 3 for i in range(nq)]
+    mg = sh.make_mask_groups(allows, group_of)
+    assert len(mg) == 3 and sh._group_large_k_serves(k, mg)
+    matmul = []
+    real = HbmIndexShard._search_matmul
+    monkeypatch.setattr(HbmIndexShard, "_search_matmul",
+                        lambda self, *a, **kw: (matmul.append(1), real(self, *a, **kw))[1])
+    calls = _count(monkeypatch)
+    s, r = sh.search(q, k, allow=mg)
+    torch.cuda.synchronize()
+    assert calls["chunk"] == [nq] and calls["emit"] == [nq]
+    ovf = int(sh._filter_large_k_last[1]) if not calls["masked"] else 1
+    print(f"LATTICE grouped large k D={D} {family}: ovf={ovf} loop={len(calls['masked'])}")
+    if family != "orthant":
+        assert ovf == 0
+    if not ovf:
+        assert not calls["masked"] and not matmul
+    per_query = torch.stack(allows)[torch.tensor(group_of, device=DEV)]
+    L.check_exact(s, r, x, q, k, per_query, what=f"grouped large k D={D} {family}")
+
+
+# 9 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", [256, 768])
+def test_tombstones_under_grouped_masks(D, monkeypatch):
+    """A MaskGroups from before a delete is refused; a fresh one is exact over allow & alive and
+    returns no dead row, under both delete routes."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    n, k, nq = N_BIG, 100, 70
+    sh = HbmIndexShard(D, n + 100, device=DEV, dtype="fp8")
+    sh.fill_random(n, seed=71 + D)
+    sh.FP8_LARGE_K_MIN_ROWS = 0
+    q = _queries(nq, D, seed=72)
+    _, qd = _quant(q)
+    rows = sh.unit_rows()[:n].clone()
+    rng = np.random.default_rng(63)
+    allows = [torch.from_numpy(rng.random(n) < 0.5) for _ in range(3)]
+    group_of = [(i // 32) % 3 for i in range(nq)]
+    mg = sh.make_mask_groups([a.to(DEV) for a in allows], group_of)
+    s, r = sh.search(q, k, allow=mg)
+    dead = torch.from_numpy(rng.random(n) < 0.1)
+    dead[64 * 100:64 * 105] = True                          # a run of whole tiles
+    dead[r[:, :5].long().flatten().cpu()] = True            # and every query's five best rows
+    sh.delete_rows(torch.nonzero(dead).flatten())
+    with pytest.raises(ValueError, match="before a delete"):
+        sh.search(q, k, allow=mg)
+    alive = ~dead
+    want = [(a & alive).to(DEV) for a in allows]
+    for route in ("zero", "mask"):
+        sh.delete_route = route
+        mg2 = sh.make_mask_groups([a.to(DEV) for a in allows], group_of)
+        with monkeypatch.context() as m:
+            calls = _count(m)
+            _bar(m, "_search_masked", "_search_matmul")
+            s2, r2 = sh.search(q, k, allow=mg2)
+        assert calls["chunk"] == [nq]
+        what = f"D={D} {route}"
+        assert not bool(dead.to(DEV)[r2.long().clamp_min(0)].any()), f"{what}: a dead row"
+        _check_out(s2, r2, rows, qd, k, want, group_of, what, True)
+
+
+# 10 -----------------------------------------------------------------------------------------------
+def test_the_default_gate(monkeypatch):
+    """Untouched attributes: the class constants are what they were; a shard of 20 011 rows still
+    loops at k = 40 under MaskGroups; one of 2^20 + 999 rows takes the new route."""
+    from codename_symbiont_amd.index.shard import HbmIndexShard
+
+    assert HbmIndexShard.FP8_LARGE_K_MIN_ROWS == HbmIndexShard.SEED_MIN_ROWS == 1 << 20
+    assert HbmIndexShard.GROUP_SCAN_MIN_GROUPS == 2 and HbmIndexShard.K_MAX_HIP == 128
+    assert HbmIndexShard.LARGE_K_CAP == 16384
+    assert (HbmIndexShard.GROUP_LOOP_MAX_GROUPS, HbmIndexShard.GROUP_LOOP_MIN_TILES) == (4, 16384)
+    D, nq = 256, 8
+    q = _queries(nq, D, seed=81)
+    _, qd = _quant(q)
+    group_of = [i % 3 for i in range(nq)]
+
+    small = HbmIndexShard(D, N_BIG + 100, device=DEV, dtype="fp8")
+    small.fill_random(N_BIG, seed=83)
+    rng = np.random.default_rng(84)
+    allows_d = [torch.from_numpy(rng.random(N_BIG) < 0.3).to(DEV) for _ in range(3)]
+    mg = small.make_mask_groups(allows_d, group_of)
+    assert "FP8_LARGE_K_MIN_ROWS" not in small.__dict__ and not small._group_large_k_serves(40, mg)
+    with monkeypatch.context() as m:
+        calls = _count(m)
+        s, r = small.search(q, 40, allow=mg)
+    assert len(calls["masked"]) == 3 and calls["chunk"] == [] and calls["emit"] == []
+    # (the loop's matmul scores float(q) . decode(x): the reference takes the queries as they are)
+    _check_out(s, r, small.unit_rows()[:N_BIG], q.float(), 40, allows_d, group_of, "small", True)
+    del small
+
+    k = 100
+    big = HbmIndexShard(D, N_GATE + 100, device=DEV, dtype="fp8")
+    big.fill_random(N_GATE, seed=82)
+    rng = np.random.default_rng(85)
+    allows_d = [torch.from_numpy(rng.random(N_GATE) < share).to(DEV) for share in (0.5, 0.05, 0.3)]
+    mg = big.make_mask_groups(allows_d, group_of)
+    assert "FP8_LARGE_K_MIN_ROWS" not in big.__dict__ and big._group_large_k_serves(k, mg)
+    with monkeypatch.context() as m:
+        calls = _count(m)
+        _bar(m, "_search_masked", "_search_matmul")
+        s, r = big.search(q, k, allow=mg)
+    stride = big.FILTER_LARGE_K_STRIDE
+    assert calls["chunk"] == [nq] and calls["emit"] == [nq]
+    assert calls["seed"] == [(16, stride * big.FILTER_LARGE_K_COARSE), (32, stride)]
+    assert int(big._filter_large_k_last[1]) == 0
+    _check_out(s, r, big.unit_rows()[:N_GATE], qd, k, allows_d, group_of, "big", True)
+
+
+# 11 -----------------------------------------------------------------------------------------------
+def test_vector_store_filter_list_at_k_100(monkeypatch):
+    """VectorStore.search(queries, 100, filter=[...]) with None entries mixed in, on a shard of
+    2^20 + 999 rows with nothing lowered: one search per request gives the same answers, and the
+    filtered entries run with the single-mask search barred."""
+    from codename_symbiont_amd.index.filter import Filter
+    from codename_symbiont_amd.index.shard import Payload
+    from codename_symbiont_amd.index.store import VectorStore
+
+    D, k = 256, 100
+    sizes = {"doc-a": 5, "doc-b": 40, "doc-c": 300, "doc-d": 700}
+    st = VectorStore(D, N_GATE + 100, device="cuda", dtype="fp8")
+    st.shard.fill_random(N_GATE - sum(sizes.values()), seed=91)     # rows without payloads
+    rng = np.random.default_rng(12)
+    ids, pls = [], []
+    for doc, m in sizes.items():
+        for j in range(m):
+            ids.append(f"{doc}/{j}")
+            pls.append(Payload(doc, f"http://{doc}.example", f"s{j}", j, "m", 0))
+    order = rng.permutation(len(ids))
+    ids, pls = [ids[i] for i in order], [pls[i] for i in order]
+    st.upsert(ids, rng.standard_normal((len(ids), D)).astype(np.float32), pls)
+    assert st.shard.visible == N_GATE and "FP8_LARGE_K_MIN_ROWS" not in st.shard.__dict__
+    only = lambda doc: Filter(must={"original_document_id": doc})
+    but = lambda doc: Filter(must_not={"original_document_id": doc})
+    flts = [only("doc-a"), None, but("doc-d"), only("doc-c"), but("doc-c"), None, only("doc-a"),
+            but("doc-d"), only("doc-b"), but("doc-a")]
+    q = rng.standard_normal((len(flts), D)).astype(np.float32)
+    s, r = st.search(q, k, filter=flts)
+    assert s.shape == (len(flts), k) and r.shape == (len(flts), k)
+    for i, f in enumerate(flts):
+        si, ri = st.search(q[i], k, filter=f)
+        fin = np.isfinite(si[0])
+        assert np.array_equal(np.isfinite(s[i]), fin) and (r[i][~fin] == -1).all(), i
+        if f is not None:
+            # the single-mask emitting search of this request alone: the same bits
+            assert np.array_equal(s[i], si[0]), i
+        else:
+            # (an unfiltered search picks its route by the batch: the standing tolerance)
+            assert np.allclose(s[i][fin], si[0][fin], rtol=0, atol=2e-3), i
+        tie = np.zeros(k, bool)
+        tie[1:] |= si[0][1:] == si[0][:-1]
+        tie[:-1] |= si[0][:-1] == si[0][1:]
+        tie[-1] |= bool(fin[-1])          # (a run of equal scores can go on past k)
+        assert ((r[i] == ri[0]) | tie | (f is None)).all(), i
+    assert int(np.isfinite(s[0]).sum()) == 5 and int(np.isfinite(s[8]).sum()) == 40
+    assert all(st.lookup(int(g))[1].original_document_id == "doc-c" for g in r[3])
+    # the route really taken: no filtered entry goes through a single-mask search or the matmul
+    rest = [i for i, f in enumerate(flts) if f is not None]
+    with monkeypatch.context() as m:
+        calls = _count(m)
+        _bar(m, "_search_masked", "_search_matmul")
+        s2, r2 = st.search(q[rest], k, filter=[flts[i] for i in rest])
+    assert calls["chunk"] == [len(rest)] and calls["emit"] == [len(rest)]
+    assert np.array_equal(s2, s[rest])
+
+
+# 12 -----------------------------------------------------------------------------------------------
+def test_wrapper_validation(monkeypatch):
+    """Every refusal is raised before any launch."""
+    from codename_symbiont_amd.ops import kernels as K
+    from codename_symbiont_amd.ops import _ext
+
+    assert hasattr(_ext.hip(), "index_scan_emit_group_fp8")
+    D, n, nq, cap, n_rblk = 384, N_SMALL, 20, 64, 5
+    sh, _ = _shard(D, n)
+    q = _queries(nq, D)
+    q8, _ = _quant(q)
+    nw = (n + 63) // 64
+    ones = torch.ones(n, dtype=torch.bool)
+    mask8, qgroup, tiles, n_live = _group_inputs([ones, ones], [i % 2 for i in range(nq)], n)
+    thr = torch.full((nq,), math.inf, device=DEV)
+    cs = torch.empty(nq, cap, device=DEV)
+    ci = torch.empty(nq, cap, dtype=torch.int32, device=DEV)
+    cn = torch.full((nq,), SENT_N, dtype=torch.int32, device=DEV)
+    launched = []
+    real = _ext.hip().index_scan_emit_group_fp8
+
+    class Spy:
+        def __getattr__(self, name):
+            if name == "index_scan_emit_group_fp8":
+                return lambda *a, **kw: launched.append(1) or real(*a, **kw)
+            return getattr(_ext.hip(), name)
+
+    spy = Spy()
+    monkeypatch.setattr(K, "hip", lambda: spy)
+
+    def call(**kw):
+        a = dict(rows_u8=sh.rows, n_valid=n, mask8=mask8, qgroup=qgroup, tiles=tiles,
+                 n_live=n_live, q_e4m3=q8, thr=thr, cand_s=cs, cand_i=ci, cand_n=cn, cap=cap,
+                 n_rblk=n_rblk)
+        a.update(kw)
+        K.index_scan_emit_group_fp8(**a)
+
+    wide = torch.zeros(n + 100, 320, dtype=torch.uint8, device=DEV)
+    u8 = lambda *shape: torch.zeros(*shape, dtype=torch.uint8, device=DEV)
+    for what, exc, kw in (
+            ("width", ValueError, dict(rows_u8=wide, q_e4m3=u8(nq, 320))),
+            ("query width", ValueError, dict(q_e4m3=u8(nq, 256))),
+            ("bf16 rows", ValueError, dict(rows_u8=torch.zeros(n + 100, D, dtype=torch.bfloat16,
+                                                               device=DEV))),
+            ("bf16 queries", ValueError, dict(q_e4m3=q)),
+            ("int32 mask8", TypeError, dict(mask8=mask8.to(torch.int32))),
+            ("four slots", ValueError, dict(mask8=torch.zeros(nw, 4, dtype=torch.int64, device=DEV))),
+            ("single-mask layout", ValueError, dict(mask8=mask8[:, 0].contiguous())),
+            ("mask8 not contiguous", ValueError,
+             dict(mask8=torch.zeros(8, nw, dtype=torch.int64, device=DEV).t())),
+            ("short mask8", ValueError, dict(mask8=mask8[:nw - 1])),
+            ("int64 qgroup", TypeError, dict(qgroup=qgroup.long())),
+            ("short qgroup", ValueError, dict(qgroup=qgroup[:nq - 1])),
+            ("long qgroup", ValueError, dict(qgroup=torch.zeros(nq + 1, dtype=torch.int32,
+                                                                device=DEV))),
+            ("host qgroup", ValueError, dict(qgroup=qgroup.cpu())),
+            ("short slab", ValueError, dict(rows_u8=sh.rows[:n])),
+            ("n_valid past the slab", ValueError, dict(n_valid=sh.rows.shape[0] + 64)),
+            ("short tile list", ValueError, dict(tiles=tiles[:-1])),
+            ("thr shorter than the batch", ValueError, dict(thr=thr[:-1])),
+            ("thr longer than the batch", ValueError, dict(thr=torch.cat([thr, thr]))),
+            ("thr f64", ValueError, dict(thr=thr.double())),
+            ("thr missing", ValueError, dict(thr=None)),
+            ("cand_n shorter than the batch", ValueError, dict(cand_n=cn[:-1])),
+            ("workspace", ValueError, dict(cand_s=cs.flatten()[:-1])),
+            ("workspace ids", ValueError, dict(cand_i=ci.flatten()[:-1])),
+            ("cap", ValueError, dict(cap=0)),
+            ("n_rblk", ValueError, dict(n_rblk=0)),
+            ("n_valid", ValueError, dict(n_valid=-1)),
+            ("int64 gate", TypeError, dict(gate=torch.zeros(1, dtype=torch.int64, device=DEV))),
+            ("2-d gate", ValueError, dict(gate=torch.zeros(1, 1, dtype=torch.int32, device=DEV))),
+            ("empty gate", ValueError, dict(gate=torch.zeros(0, dtype=torch.int32, device=DEV)))):
+        with pytest.raises(exc):
+            call(**kw)
+        assert not launched, what
+    torch.cuda.synchronize()
+    assert bool((cn == SENT_N).all())
+    call()                                             # thr = +inf: runs, emits nothing
+    torch.cuda.synchronize()
+    assert launched == [1] and not bool(cn.any())
