@@ -22,6 +22,12 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+# (neither module loads an extension when imported; the masked routes, a few launches per search,
+# use these names without a per-call import)
+from ..ops import kernels as K
+from ..ops._ext import hip, stream_handle
+from ..ops.kernels import MASK_GROUPS   # masks one grouped scan carries
+
 TILE_ROWS = 64  # scan tile: 2 MFMA sub-tiles per barrier interval
 
 
@@ -178,7 +184,7 @@ class PayloadStore:
         self.n = int(n)
 
 
-FP8_SCALE = 256.0  # == ops.kernels.FP8_SCALE (kept import-free for CPU-only users)
+FP8_SCALE = K.FP8_SCALE  # 256.0: unit vectors -> |S x_i| <= 256 < 448 (e4m3 max)
 
 
 def resolve_prune(mode: str | None, dtype: str = "bf16", dim: int = 384,
@@ -301,8 +307,6 @@ class RowMask:
         """Allowed rows (reads the device: diagnostics and tests)."""
         return int(_unpack_bits(self.bits).sum())
 
-
-MASK_GROUPS = 8   # masks one grouped scan carries (index_filter_group.hip, ..._group_fp8.hip)
 
 
 class MaskGroups:
@@ -1618,6 +1622,19 @@ class HbmIndexShard:
         """Some masked scan of this shard walks a RowMask's live-tile list."""
         return self._filter_scan_serves() or self._filter_large_k_serves(self.K_MAX_HIP)
 
+    def _empty_result(self, NQ: int, k: int):
+        """The result of a search with no queries or k <= 0."""
+        return (torch.empty(NQ, max(k, 0), device=self.device),
+                torch.empty(NQ, max(k, 0), dtype=torch.int32, device=self.device))
+
+    def _refuse_stale(self, device, dead_gen: int) -> None:
+        """Refuse a RowMask (or MaskGroups) of another device or from before a delete."""
+        if device != self.device:
+            raise ValueError(f"RowMask on {device}, shard on {self.device}")
+        if dead_gen != self.dead_gen:
+            raise ValueError("RowMask made before a delete (it may allow a deleted row): make "
+                             "it again with make_mask")
+
     def _search_masked(self, q_unit, k: int, n_cus, allow):
         """``search`` under a row mask, exact over the allowed rows.  A GPU shard at k <= 32 takes
         the masked list scan of its row format (bf16 at a width in FILTER_DIMS, fp8 at one in
@@ -1632,14 +1649,9 @@ class HbmIndexShard:
         NQ = q_unit.shape[0]
         k = int(k)
         if NQ == 0 or k <= 0:
-            return (torch.empty(NQ, max(k, 0), device=self.device),
-                    torch.empty(NQ, max(k, 0), dtype=torch.int32, device=self.device))
+            return self._empty_result(NQ, k)
         mask = self.make_mask(allow)
-        if mask.bits.device != self.device:
-            raise ValueError(f"RowMask on {mask.bits.device}, shard on {self.device}")
-        if mask.dead_gen != self.dead_gen:
-            raise ValueError("RowMask made before a delete (it may allow a deleted row): make "
-                             "it again with make_mask")
+        self._refuse_stale(mask.bits.device, mask.dead_gen)
         if (self.device.type == "cuda" and self._filter_scan_serves() and k <= 32
                 and mask.tiles is not None):
             return self._search_filtered(q_unit.to(torch.bfloat16).contiguous(), k, mask, n_cus)
@@ -1673,11 +1685,7 @@ class HbmIndexShard:
                 by_obj[id(m)] = self.make_mask(m)
             made.append(by_obj[id(m)])
         for m in made:
-            if m.bits.device != self.device:
-                raise ValueError(f"RowMask on {m.bits.device}, shard on {self.device}")
-            if m.dead_gen != self.dead_gen:
-                raise ValueError("RowMask made before a delete (it may allow a deleted row): "
-                                 "make it again with make_mask")
+            self._refuse_stale(m.bits.device, m.dead_gen)
             if m.visible != made[0].visible or m.bits.numel() != made[0].bits.numel():
                 raise ValueError("make_mask_groups: masks made at different visible rows")
         # merge: the same RowMask object first, then equal bits (one unique over the distinct
@@ -1708,21 +1716,16 @@ class HbmIndexShard:
         """The grouped masked list scan serves this search (bf16: index_filter_group.hip; fp8:
         index_filter_group_fp8.hip, built at every width and both kmax of the single-mask fp8
         scan)."""
-        if (self.device.type != "cuda" or not 0 < k <= 32
-                or len(groups) < self.GROUP_SCAN_MIN_GROUPS):
-            return False
-        return ((self.dtype == "bf16" and self.dim in FILTER_DIMS)
-                or (self.dtype == "fp8" and self.dim in FILTER_FP8_DIMS))
+        return (self.device.type == "cuda" and 0 < k <= 32
+                and len(groups) >= self.GROUP_SCAN_MIN_GROUPS and self._filter_scan_serves())
 
     def _group_large_k_serves(self, k: int, groups: MaskGroups) -> bool:
         """The grouped emitting e4m3 scan (index_emit_group_fp8.hip) serves this search: an fp8
-        shard on a GPU at a width in FILTER_LARGE_K_FP8_DIMS, 32 < k <= K_MAX_HIP, with
-        FP8_LARGE_K_MIN_ROWS visible rows or more (the single-mask route's own gate: below it
-        the per-mask loop's matmul keeps the search) and GROUP_SCAN_MIN_GROUPS masks or more."""
-        return (self.device.type == "cuda" and self.dtype == "fp8"
-                and self.dim in FILTER_LARGE_K_FP8_DIMS and 32 < k <= self.K_MAX_HIP
-                and self.visible >= self.FP8_LARGE_K_MIN_ROWS
-                and len(groups) >= self.GROUP_SCAN_MIN_GROUPS)
+        shard the single-mask emitting scan serves at this k (_filter_large_k_serves: its
+        FP8_LARGE_K_MIN_ROWS gate too, below which the per-mask loop's matmul keeps the search)
+        with GROUP_SCAN_MIN_GROUPS masks or more."""
+        return (self.dtype == "fp8" and len(groups) >= self.GROUP_SCAN_MIN_GROUPS
+                and self._filter_large_k_serves(k))
 
     def _search_grouped(self, q_unit, k: int, n_cus, groups: MaskGroups):
         """``search`` under a mask per query, each query exact over its own mask's rows.
@@ -1753,14 +1756,9 @@ class HbmIndexShard:
         k = int(k)
         if len(groups.group_of) != NQ:
             raise ValueError(f"MaskGroups for {len(groups.group_of)} queries, search has {NQ}")
-        if groups.device != self.device:
-            raise ValueError(f"RowMask on {groups.device}, shard on {self.device}")
-        if groups.dead_gen != self.dead_gen:
-            raise ValueError("RowMask made before a delete (it may allow a deleted row): make "
-                             "it again with make_mask")
+        self._refuse_stale(groups.device, groups.dead_gen)
         if NQ == 0 or k <= 0:
-            return (torch.empty(NQ, max(k, 0), device=self.device),
-                    torch.empty(NQ, max(k, 0), dtype=torch.int32, device=self.device))
+            return self._empty_result(NQ, k)
         if len(groups) == 1:
             return self._search_masked(q_unit, k, n_cus, groups.masks[0])
         out_s = torch.empty(NQ, k, device=self.device)
@@ -1824,60 +1822,103 @@ class HbmIndexShard:
     GROUP_LOOP_LARGE_K_SCAN_DIMS = (384,)
 
     def _loop_keeps_chunk(self, ch: dict, k: int) -> bool:
-        from ..ops._ext import hip
-
         live = ch["live"]
         if live is None or not 2 <= len(ch["nq_of"]) <= self.GROUP_LOOP_MAX_GROUPS:
             return False
         if k > 32 and self.dim in self.GROUP_LOOP_LARGE_K_SCAN_DIMS:
             return False
-        # queries per block of the scans: 256 on fp8 (the rule can then hold above 256 queries
-        # only), topk_geometry's on bf16
-        qpb = 256 if self.dtype == "fp8" else hip().topk_geometry(
-            self.dim, 16 if k <= 16 else 32)[1]
+        # queries per block of the list scans (256 on fp8: the rule can then hold above 256
+        # queries only)
+        qpb = self._masked_format()[0](16 if k <= 16 else 32)[1]
         blocks = lambda nq: (nq + qpb - 1) // qpb
         union = live[-1]
         return (blocks(sum(ch["nq_of"])) > max(blocks(nq) for nq in ch["nq_of"])
                 and union >= self.GROUP_LOOP_MIN_TILES and union >= 0.9 * sum(live[:-1]))
 
-    def _search_group_chunk(self, q_unit, k: int, groups: MaskGroups, ch: dict, n_cus):
-        """The grouped masked list scan over one chunk's queries + merge: _search_filtered with
-        the chunk's eight mask words per tile and the union's live-tile list (same grid sizing,
-        same seed pass, whose k-th best per query is a lower bound under that query's own
-        mask).  On an fp8 shard ``q_unit`` holds the queries' e4m3 bytes (quantised once per
-        search by _search_grouped), and the raw scores, S^2 * cosine, are rescaled once at the
-        end."""
-        from ..ops import kernels as K
-        from ..ops._ext import hip, stream_handle
+    # ------------------------------------------------------------------ the masked scans' bodies
+    # One list-scan body and one large-k body serve every masked route.  They take what differs
+    # between the routes as values: the kernels (_masked_kernels), the mask operands the
+    # wrappers take between ``n_valid`` and the queries -- (words, tiles, n_live) of a RowMask,
+    # (mask8, qgroup, tiles, n_live) of a MaskGroups chunk -- the queries as the kernels read
+    # them, and the row format's own numbers (_masked_format).
+    def _masked_kernels(self, grouped: bool):
+        """(list scan, emitting scan) of this shard's row format, under one mask or a mask per
+        query (bf16 has no grouped emitting scan)."""
+        if self.dtype == "fp8":
+            return ((K.index_scan_filter_group_fp8, K.index_scan_emit_group_fp8) if grouped
+                    else (K.index_scan_filter_fp8, K.index_scan_emit_fp8))
+        return ((K.index_scan_filter_group, None) if grouped
+                else (K.index_scan_filter, K.index_scan_mq_filter))
 
+    def _masked_format(self):
+        """What the masked bodies take from the row format, (geometry, emit_form, threshold,
+        rescale): ``geometry(kmax)`` -> (lists, queries per block) of the list scan;
+        ``emit_form(NQ)`` -> (queries per block, extra arguments) of the emitting scan;
+        ``threshold(cand_s, k)`` -> T from a seed pass's candidates; ``rescale``: the factor
+        from raw scores to cosines, or None."""
+        if self.dtype == "fp8":
+            # 2 lists and 256 queries per block at every width and kmax.  All e4m3 kernels run
+            # one MFMA chain, so a row's raw score (S^2 * cosine) is the same bits in each: T is
+            # the k-th largest finite raw candidate less one ulp, with no margin.
+            return (lambda kmax: (2, 256), lambda NQ: (256, ()), filter_large_k_threshold_ulp,
+                    1.0 / (FP8_SCALE * FP8_SCALE))
+        h = hip()
+
+        def emit_form(NQ):
+            form = self._mq_filter_form(NQ)
+            return h.mq_queries_per_blk(*form), form
+
+        # (MQ_THR_MARGIN: the list scan and the emitting scan sum in different orders)
+        return (lambda kmax: h.topk_geometry(self.dim, kmax), emit_form,
+                lambda cand_s, k: filter_large_k_threshold(cand_s, k, self.MQ_THR_MARGIN), None)
+
+    def _masked_queries(self, q_unit, visible: int):
+        """The queries as this shard's masked scans read them: bf16 as they are; on an fp8 shard
+        their e4m3 bytes (an empty search launches nothing, this neither)."""
+        if self.dtype != "fp8" or min(visible, self.visible) <= 0:
+            return q_unit
+        return K.quant_fp8(q_unit, scale=FP8_SCALE)
+
+    def _masked_rblk(self, n: int, NQ: int, qpb: int, n_cus) -> int:
+        """Row slots per query block of a masked scan's grid: the CUs shared among the query
+        blocks, with FILTER_MIN_TILES tiles or more to a slot."""
+        if n_cus is None:
+            n_cus = self._n_cus()
+        return max(1, min(math.ceil(n / (TILE_ROWS * self.FILTER_MIN_TILES)),
+                          max(1, round(n_cus / math.ceil(NQ / qpb)))))
+
+    def _masked_list_scan(self, scan, visible: int, operands: tuple, q, k: int, n_cus, gate=None):
+        """The masked list scan ``scan`` + merge, k <= 32, over the rows below ``visible`` that
+        ``operands`` allow.  The grid and the candidate workspace are sized as if every tile
+        were live; the kernel reads the live count on the device.  ``filter_seed``: a first pass
+        over every FILTER_SEED_STRIDE-th live tile of each workgroup's slice sees allowed rows
+        only (under a mask per query: rows of that query's own mask), so its k-th best is a
+        lower bound on the final k-th allowed score (-inf where it found fewer than k rows); the
+        full pass starts from it.  Exact either way.  ``gate`` (int32 device flag): every scan
+        and merge launch runs only if it is non-zero (the outputs are then left unwritten; the
+        torch glue between the passes runs on whatever they hold).  Raw e4m3 scores are rescaled
+        once at the end."""
         h, dev = hip(), self.device
-        NQ = q_unit.shape[0]
+        NQ = q.shape[0]
         kmax = 16 if k <= 16 else 32
-        n = min(groups.visible, self.visible)
+        n = min(visible, self.visible)
         out_s = torch.empty(NQ, k, device=dev)
         out_i = torch.empty(NQ, k, dtype=torch.int32, device=dev)
         if n <= 0:
             return out_s.fill_(-math.inf), out_i.fill_(-1)
-        fp8 = self.dtype == "fp8"
-        if fp8:
-            scan, (lists, qpb) = K.index_scan_filter_group_fp8, (2, 256)
-        else:
-            scan, (lists, qpb) = K.index_scan_filter_group, h.topk_geometry(self.dim, kmax)
-        n_qblk = math.ceil(NQ / qpb)
-        if n_cus is None:
-            n_cus = self._n_cus()
-        n_rblk = max(1, min(math.ceil(n / (TILE_ROWS * self.FILTER_MIN_TILES)),
-                            max(1, round(n_cus / n_qblk))))
+        geometry, _, _, rescale = self._masked_format()
+        lists, qpb = geometry(kmax)
+        n_rblk = self._masked_rblk(n, NQ, qpb, n_cus)
         ncand = n_rblk * lists * kmax
         cs = torch.empty(NQ, ncand, device=dev)
         ci = torch.empty(NQ, ncand, dtype=torch.int32, device=dev)
         st = stream_handle(dev)
 
         def one_pass(thr, stride):
-            scan(self.rows, n, ch["mask8"], ch["qgroup"], ch["tiles"], ch["n_live"], q_unit,
-                 kmax, n_rblk, cs, ci, thr, stride, self.scan_xcd)
+            scan(self.rows, n, *operands, q, kmax, n_rblk, cs, ci, thr, stride, self.scan_xcd,
+                 gate)
             h.topk_merge(cs.data_ptr(), ci.data_ptr(), NQ, ncand, kmax, k, out_s.data_ptr(),
-                         out_i.data_ptr(), 0, 0, st, 0)
+                         out_i.data_ptr(), 0, 0, st, 0 if gate is None else gate.data_ptr())
 
         thr = None
         if self.filter_seed:
@@ -1885,9 +1926,24 @@ class HbmIndexShard:
             kth = out_s[:, k - 1].contiguous()
             thr = torch.nextafter(kth, torch.full_like(kth, -math.inf))
         one_pass(thr, 1)
-        if fp8:
-            out_s.mul_(1.0 / (FP8_SCALE * FP8_SCALE))   # (-inf stays -inf)
+        if rescale is not None:
+            out_s.mul_(rescale)   # (-inf stays -inf)
         return out_s, out_i
+
+    def _search_filtered(self, q_unit, k: int, mask: RowMask, n_cus, gate=None):
+        """The masked list scan + merge under one RowMask (index_filter.hip; index_filter_fp8.hip
+        on an fp8 shard, whose queries are quantised to e4m3 here)."""
+        return self._masked_list_scan(
+            self._masked_kernels(False)[0], mask.visible, (mask.words, mask.tiles, mask.n_live),
+            self._masked_queries(q_unit, mask.visible), k, n_cus, gate)
+
+    def _search_group_chunk(self, q_unit, k: int, groups: MaskGroups, ch: dict, n_cus):
+        """The grouped masked list scan + merge over one chunk's queries: the chunk's eight mask
+        words per tile and the union's live-tile list.  On an fp8 shard ``q_unit`` holds the
+        queries' e4m3 bytes (quantised once per search by _search_grouped)."""
+        return self._masked_list_scan(
+            self._masked_kernels(True)[0], groups.visible,
+            (ch["mask8"], ch["qgroup"], ch["tiles"], ch["n_live"]), q_unit, k, n_cus)
 
     # seed pass of the masked large-k search: every S-th live tile of each workgroup's slice.
     # 32 is the unmasked route's sample rate (PRUNE_TILE_SHIFT = 5).  A query emits about k * S
@@ -1900,68 +1956,6 @@ class HbmIndexShard:
     # extra launch where the lists hardly fill); same T, same candidates (profiles/r11_filter_largek/)
     FILTER_LARGE_K_COARSE = 16
 
-    def _search_group_chunk_large_k(self, q8, k: int, groups: MaskGroups, ch: dict, n_cus,
-                                    seed: bool = True):
-        """_filtered_large_k_fp8 under a mask per query, over one chunk's queries (``q8``: their
-        e4m3 bytes, quantised once per search by _search_grouped): the same grid, the grouped
-        e4m3 list scan (index_filter_group_fp8.hip) as the seed pass at kmax 32 over every
-        FILTER_LARGE_K_STRIDE-th tile of the union's list -- itself seeded at kmax 16 and stride
-        x FILTER_LARGE_K_COARSE from SEED_MIN_ROWS rows on -- and the grouped emitting scan
-        (index_emit_group_fp8.hip) over the whole list.  A query's seed candidates are rows of
-        its own mask only, so T (filter_large_k_threshold_ulp: all three kernels run one MFMA
-        chain) is a lower bound on its k-th best score under its own mask.  ``seed=False``:
-        T = -inf.  Returns None when a query's candidates overflow LARGE_K_CAP (the flag is
-        read once per chunk); the caller then answers the chunk's groups one mask at a time."""
-        from ..ops import kernels as K
-        from ..ops._ext import hip, stream_handle
-
-        h, dev = hip(), self.device
-        NQ = q8.shape[0]
-        n = min(groups.visible, self.visible)
-        out_s = torch.empty(NQ, k, device=dev)
-        out_i = torch.empty(NQ, k, dtype=torch.int32, device=dev)
-        if n <= 0:
-            return out_s.fill_(-math.inf), out_i.fill_(-1)
-        if n_cus is None:
-            n_cus = self._n_cus()
-        tile_slots = math.ceil(n / (TILE_ROWS * self.FILTER_MIN_TILES))
-        n_qblk = math.ceil(NQ / 256)
-        n_rblk = max(1, min(tile_slots, max(1, round(n_cus / n_qblk))))
-        mask8, qgroup, tiles, n_live = ch["mask8"], ch["qgroup"], ch["tiles"], ch["n_live"]
-        if seed:
-            cs = torch.empty(NQ, n_rblk * 2 * 32, device=dev)
-            ci = torch.empty(NQ, n_rblk * 2 * 32, dtype=torch.int32, device=dev)
-            T0 = None
-            if self.FILTER_LARGE_K_COARSE > 1 and n >= self.SEED_MIN_ROWS:
-                # the seed pass's own seed: a subset of its sample, so T is unchanged
-                c0 = torch.empty(NQ, n_rblk * 2 * 16, device=dev)
-                i0 = torch.empty(NQ, n_rblk * 2 * 16, dtype=torch.int32, device=dev)
-                K.index_scan_filter_group_fp8(
-                    self.rows, n, mask8, qgroup, tiles, n_live, q8, 16, n_rblk, c0, i0, None,
-                    self.FILTER_LARGE_K_STRIDE * self.FILTER_LARGE_K_COARSE, self.scan_xcd)
-                T0 = filter_large_k_threshold_ulp(c0, k)
-            K.index_scan_filter_group_fp8(self.rows, n, mask8, qgroup, tiles, n_live, q8, 32,
-                                          n_rblk, cs, ci, T0, self.FILTER_LARGE_K_STRIDE,
-                                          self.scan_xcd)
-            T = filter_large_k_threshold_ulp(cs, k)
-        else:
-            T = torch.full((NQ,), -math.inf, device=dev)
-        cap = self.LARGE_K_CAP
-        es = torch.empty(NQ, cap, device=dev)
-        ei = torch.empty(NQ, cap, dtype=torch.int32, device=dev)
-        cnt = torch.empty(NQ, dtype=torch.int32, device=dev)
-        ovf = torch.zeros(1, dtype=torch.int32, device=dev)
-        K.index_scan_emit_group_fp8(self.rows, n, mask8, qgroup, tiles, n_live, q8, T, es, ei,
-                                    cnt, cap, n_rblk, self.scan_xcd)
-        h.topk_select_counted(es.data_ptr(), ei.data_ptr(), cnt.data_ptr(), cap, NQ, 128, k,
-                              out_s.data_ptr(), out_i.data_ptr(), ovf.data_ptr(),
-                              stream_handle(dev), gate=0, reset_ovf=False)
-        out_s.mul_(1.0 / (FP8_SCALE * FP8_SCALE))   # (-inf stays -inf)
-        self._filter_large_k_last = (cnt, ovf)   # candidate counts / overflow flag (tests)
-        if int(ovf.item()):
-            return None
-        return out_s, out_i
-
     def _mq_filter_form(self, NQ: int):
         """(sets, rsplit) of the masked emitting scan: _mq_form's, except that at D = 384 below
         512 queries it is always the row-split form (there is no masked (2, 1) form)."""
@@ -1969,53 +1963,43 @@ class HbmIndexShard:
             return (2 if self.dim == 768 else 1), 1
         return (4, 1) if NQ >= 512 else (4, 2)
 
-    def _search_filtered_large_k(self, q_unit, k: int, mask: RowMask, n_cus, gate=None,
-                                 seed: bool = True):
-        """EXACT top-k over the allowed rows for 32 < k <= 128 (bf16, FILTER_LARGE_K_DIMS), at any
-        number of visible rows:
+    def _masked_large_k(self, scan, emit, visible: int, operands: tuple, q, k: int, n_cus,
+                        gate=None, seed: bool = True):
+        """EXACT top-k for 32 < k <= 128 over the rows below ``visible`` that ``operands``
+        allow, at any number of visible rows; ``scan`` / ``emit``: the masked list scan and the
+        masked emitting scan of the row format (_masked_kernels).
 
         1. T[q], a lower bound on query q's final k-th ALLOWED score from allowed rows only: the
-           masked list scan (kmax 32) over every FILTER_LARGE_K_STRIDE-th live tile of each
-           workgroup's slice leaves [NQ, n_rblk * lists * 32] candidates, each a distinct allowed
-           row's real score, and T is the k-th largest finite one (-inf below k of them: a mask
-           with few allowed rows emits every one), less MQ_THR_MARGIN for the two kernels'
-           different summation orders (filter_large_k_threshold).  On shards of SEED_MIN_ROWS
-           rows or more that pass is itself seeded, by a kmax = 16 pass over every
-           FILTER_LARGE_K_COARSE-th tile of its sample, which changes its time and not T.
+           list scan (kmax 32) over every FILTER_LARGE_K_STRIDE-th live tile of each workgroup's
+           slice leaves [NQ, n_rblk * lists * 32] candidates, each a distinct allowed row's real
+           score (under a mask per query: a row of that query's own mask), and T is the k-th
+           largest finite one (-inf below k of them: a mask with few allowed rows emits every
+           one), less what the format's two kernels may differ by (_masked_format).  On shards
+           of SEED_MIN_ROWS rows or more that pass is itself seeded, by a kmax = 16 pass over
+           every FILTER_LARGE_K_COARSE-th tile of its sample, which changes its time and not T.
            ``seed=False``: T = -inf.
-        2. the masked emitting scan (index_mq_filter.hip) over the whole list keeps every allowed
-           row above T in LARGE_K_CAP slots per query, and the radix select takes the top k:
-           descending, (-inf, -1) past the allowed rows.
+        2. the emitting scan over the whole list keeps every allowed row above T in LARGE_K_CAP
+           slots per query, and the radix select takes the top k: descending, (-inf, -1) past
+           the allowed rows.  Raw e4m3 scores are rescaled once, after the select.
         3. a query whose candidates overflow the cap raises the select's flag (read back once,
-           as _search_large_k reads its own) and the search takes the masked matmul.
+           as _search_large_k reads its own): the body then returns None, and its caller
+           answers by a route without a cap.
 
         ``gate`` (int32 device flag): every launch runs only if it is non-zero; at 0 the
-        overflow flag stays 0 and the outputs hold garbage the caller never selects.
-
-        An fp8 shard (FILTER_LARGE_K_FP8_DIMS) runs the same three steps on its own kernels
-        (_filtered_large_k_fp8)."""
-        from ..ops import kernels as K
-        from ..ops._ext import hip, stream_handle
-
+        overflow flag stays 0 and the outputs hold garbage the caller never selects."""
         h, dev = hip(), self.device
-        NQ = q_unit.shape[0]
-        n = min(mask.visible, self.visible)
+        NQ = q.shape[0]
+        n = min(visible, self.visible)
         out_s = torch.empty(NQ, k, device=dev)
         out_i = torch.empty(NQ, k, dtype=torch.int32, device=dev)
         if n <= 0:
             return out_s.fill_(-math.inf), out_i.fill_(-1)
-        if n_cus is None:
-            n_cus = self._n_cus()
-        tile_slots = math.ceil(n / (TILE_ROWS * self.FILTER_MIN_TILES))
-        if self.dtype == "fp8":
-            return self._filtered_large_k_fp8(q_unit, k, mask, n, n_cus, tile_slots, gate, seed,
-                                              out_s, out_i)
+        geometry, emit_form, threshold, rescale = self._masked_format()
         if seed:
-            lists, qpb = h.topk_geometry(self.dim, 32)
-            n_rblk = max(1, min(tile_slots, max(1, round(n_cus / math.ceil(NQ / qpb)))))
-            ncand = n_rblk * lists * 32
-            cs = torch.empty(NQ, ncand, device=dev)
-            ci = torch.empty(NQ, ncand, dtype=torch.int32, device=dev)
+            lists, qpb = geometry(32)
+            n_rblk = self._masked_rblk(n, NQ, qpb, n_cus)
+            cs = torch.empty(NQ, n_rblk * lists * 32, device=dev)
+            ci = torch.empty(NQ, n_rblk * lists * 32, dtype=torch.int32, device=dev)
             T0 = None
             if self.FILTER_LARGE_K_COARSE > 1 and n >= self.SEED_MIN_ROWS:
                 # The seed pass's register lists start empty and take their first rows through
@@ -2024,148 +2008,68 @@ class HbmIndexShard:
                 # subset of it) gives the seed pass a threshold of its own; the seed pass's
                 # k best rows all lie above it, so T is what the unseeded seed pass gives.
                 # (Not on small shards, where its launch costs more than it saves.)
-                l16, _ = h.topk_geometry(self.dim, 16)
+                l16, _ = geometry(16)
                 c0 = torch.empty(NQ, n_rblk * l16 * 16, device=dev)
                 i0 = torch.empty(NQ, n_rblk * l16 * 16, dtype=torch.int32, device=dev)
-                K.index_scan_filter(self.rows, n, mask.words, mask.tiles, mask.n_live, q_unit,
-                                    16, n_rblk, c0, i0, None,
-                                    self.FILTER_LARGE_K_STRIDE * self.FILTER_LARGE_K_COARSE,
-                                    self.scan_xcd, gate)
-                T0 = filter_large_k_threshold(c0, k, self.MQ_THR_MARGIN)
-            K.index_scan_filter(self.rows, n, mask.words, mask.tiles, mask.n_live, q_unit, 32,
-                                n_rblk, cs, ci, T0, self.FILTER_LARGE_K_STRIDE, self.scan_xcd,
-                                gate)
-            T = filter_large_k_threshold(cs, k, self.MQ_THR_MARGIN)
+                scan(self.rows, n, *operands, q, 16, n_rblk, c0, i0, None,
+                     self.FILTER_LARGE_K_STRIDE * self.FILTER_LARGE_K_COARSE, self.scan_xcd, gate)
+                T0 = threshold(c0, k)
+            scan(self.rows, n, *operands, q, 32, n_rblk, cs, ci, T0, self.FILTER_LARGE_K_STRIDE,
+                 self.scan_xcd, gate)
+            T = threshold(cs, k)
         else:
             T = torch.full((NQ,), -math.inf, device=dev)
-        sets, rsplit = self._mq_filter_form(NQ)
-        n_qblk = math.ceil(NQ / h.mq_queries_per_blk(sets, rsplit))
-        n_rblk = max(1, min(tile_slots, max(1, round(n_cus / n_qblk))))
+        # (the emitting scan's queries per block, and so its grid, are not the list scan's)
+        qpb, form = emit_form(NQ)
+        n_rblk = self._masked_rblk(n, NQ, qpb, n_cus)
         cap = self.LARGE_K_CAP
         es = torch.empty(NQ, cap, device=dev)
         ei = torch.empty(NQ, cap, dtype=torch.int32, device=dev)
         cnt = torch.empty(NQ, dtype=torch.int32, device=dev)
         # this search's own overflow flag; zeroed here, so a closed gate leaves it 0
         ovf = torch.zeros(1, dtype=torch.int32, device=dev)
-        K.index_scan_mq_filter(self.rows, n, mask.words, mask.tiles, mask.n_live, q_unit, T, es,
-                               ei, cnt, cap, n_rblk, sets, rsplit, self.scan_xcd, gate)
+        emit(self.rows, n, *operands, q, T, es, ei, cnt, cap, n_rblk, *form, self.scan_xcd, gate)
         h.topk_select_counted(es.data_ptr(), ei.data_ptr(), cnt.data_ptr(), cap, NQ, 128, k,
                               out_s.data_ptr(), out_i.data_ptr(), ovf.data_ptr(),
                               stream_handle(dev), gate=0 if gate is None else gate.data_ptr(),
                               reset_ovf=False)
+        if rescale is not None:
+            out_s.mul_(rescale)   # (-inf stays -inf)
         self._filter_large_k_last = (cnt, ovf)   # candidate counts / overflow flag (tests)
         if int(ovf.item()):
-            return self._search_matmul(q_unit, k, mask=mask)
+            return None
         return out_s, out_i
 
-    def _filtered_large_k_fp8(self, q_unit, k: int, mask: RowMask, n: int, n_cus: int,
-                              tile_slots: int, gate, seed: bool, out_s, out_i):
-        """_search_filtered_large_k on an fp8 shard: the queries are quantised to e4m3 once; the
-        seed passes are the masked e4m3 list scan (index_filter_fp8.hip: 2 lists, 256 queries per
-        block) at the same stride and coarse stride; the emitting e4m3 scan (index_emit_fp8.hip)
-        keeps every allowed row above T.  Both kernels run one MFMA chain, so a row's raw score
-        (S^2 * cosine) is the same bits in each, and T is the k-th largest finite raw candidate
-        less one ulp, with no margin (filter_large_k_threshold_ulp).  The selected scores are
-        rescaled once at the end.  On overflow the masked matmul runs on the DECODED quantised
-        queries, so it differs from the scan by summation order only, not by the queries' e4m3
-        rounding."""
-        from ..ops import kernels as K
-        from ..ops._ext import hip, stream_handle
+    def _search_filtered_large_k(self, q_unit, k: int, mask: RowMask, n_cus, gate=None,
+                                 seed: bool = True):
+        """The masked large-k search under one RowMask (bf16: index_filter.hip and
+        index_mq_filter.hip at a width in FILTER_LARGE_K_DIMS; fp8: index_filter_fp8.hip and
+        index_emit_fp8.hip at one in FILTER_LARGE_K_FP8_DIMS, the queries quantised to e4m3
+        here).  On overflow the search takes the masked matmul -- on an fp8 shard over the
+        DECODED quantised queries, so it differs from the scan by summation order only, not by
+        the queries' e4m3 rounding."""
+        scan, emit = self._masked_kernels(False)
+        q = self._masked_queries(q_unit, mask.visible)
+        res = self._masked_large_k(scan, emit, mask.visible,
+                                   (mask.words, mask.tiles, mask.n_live), q, k, n_cus, gate, seed)
+        if res is not None:
+            return res
+        if self.dtype == "fp8":
+            q = K.fp8_to_float(q, FP8_SCALE)
+        return self._search_matmul(q, k, mask=mask)
 
-        h, dev = hip(), self.device
-        NQ = q_unit.shape[0]
-        q8 = K.quant_fp8(q_unit, scale=FP8_SCALE)
-        n_qblk = math.ceil(NQ / 256)
-        n_rblk = max(1, min(tile_slots, max(1, round(n_cus / n_qblk))))
-        if seed:
-            cs = torch.empty(NQ, n_rblk * 2 * 32, device=dev)
-            ci = torch.empty(NQ, n_rblk * 2 * 32, dtype=torch.int32, device=dev)
-            T0 = None
-            if self.FILTER_LARGE_K_COARSE > 1 and n >= self.SEED_MIN_ROWS:
-                # the seed pass's own seed, as on bf16: a subset of its sample, so T is unchanged
-                c0 = torch.empty(NQ, n_rblk * 2 * 16, device=dev)
-                i0 = torch.empty(NQ, n_rblk * 2 * 16, dtype=torch.int32, device=dev)
-                K.index_scan_filter_fp8(self.rows, n, mask.words, mask.tiles, mask.n_live, q8, 16,
-                                        n_rblk, c0, i0, None,
-                                        self.FILTER_LARGE_K_STRIDE * self.FILTER_LARGE_K_COARSE,
-                                        self.scan_xcd, gate)
-                T0 = filter_large_k_threshold_ulp(c0, k)
-            K.index_scan_filter_fp8(self.rows, n, mask.words, mask.tiles, mask.n_live, q8, 32,
-                                    n_rblk, cs, ci, T0, self.FILTER_LARGE_K_STRIDE, self.scan_xcd,
-                                    gate)
-            T = filter_large_k_threshold_ulp(cs, k)
-        else:
-            T = torch.full((NQ,), -math.inf, device=dev)
-        cap = self.LARGE_K_CAP
-        es = torch.empty(NQ, cap, device=dev)
-        ei = torch.empty(NQ, cap, dtype=torch.int32, device=dev)
-        cnt = torch.empty(NQ, dtype=torch.int32, device=dev)
-        # this search's own overflow flag; zeroed here, so a closed gate leaves it 0
-        ovf = torch.zeros(1, dtype=torch.int32, device=dev)
-        K.index_scan_emit_fp8(self.rows, n, mask.words, mask.tiles, mask.n_live, q8, T, es, ei,
-                              cnt, cap, n_rblk, self.scan_xcd, gate)
-        h.topk_select_counted(es.data_ptr(), ei.data_ptr(), cnt.data_ptr(), cap, NQ, 128, k,
-                              out_s.data_ptr(), out_i.data_ptr(), ovf.data_ptr(),
-                              stream_handle(dev), gate=0 if gate is None else gate.data_ptr(),
-                              reset_ovf=False)
-        out_s.mul_(1.0 / (FP8_SCALE * FP8_SCALE))   # (-inf stays -inf)
-        self._filter_large_k_last = (cnt, ovf)   # candidate counts / overflow flag (tests)
-        if int(ovf.item()):
-            return self._search_matmul(K.fp8_to_float(q8, FP8_SCALE), k, mask=mask)
-        return out_s, out_i
-
-    def _search_filtered(self, q_unit, k: int, mask: RowMask, n_cus, gate=None):
-        """The masked list scan (index_filter.hip; index_filter_fp8.hip on an fp8 shard, whose
-        queries are quantised to e4m3 here and whose raw scores, S^2 * cosine, are rescaled once
-        at the end) + merge.  The grid and the candidate workspace are sized as if every tile
-        were live; the kernel reads the live count on the device.  ``filter_seed``: a first pass
-        over every FILTER_SEED_STRIDE-th live tile of each workgroup's slice sees allowed rows
-        only, so its k-th best is a lower bound on the final k-th allowed score (-inf where it
-        found fewer than k rows); the full pass starts from it.  Exact either way.  ``gate`` (int32
-        device flag): every scan and merge launch runs only if it is non-zero (the outputs are
-        then left unwritten; the torch glue between the passes runs on whatever they hold)."""
-        from ..ops import kernels as K
-        from ..ops._ext import hip, stream_handle
-
-        h, dev = hip(), self.device
-        NQ = q_unit.shape[0]
-        kmax = 16 if k <= 16 else 32
-        n = min(mask.visible, self.visible)
-        out_s = torch.empty(NQ, k, device=dev)
-        out_i = torch.empty(NQ, k, dtype=torch.int32, device=dev)
-        if n <= 0:
-            return out_s.fill_(-math.inf), out_i.fill_(-1)
-        fp8 = self.dtype == "fp8"
-        if fp8:
-            q_unit = K.quant_fp8(q_unit, scale=FP8_SCALE)
-            scan, (lists, qpb) = K.index_scan_filter_fp8, (2, 256)
-        else:
-            scan, (lists, qpb) = K.index_scan_filter, h.topk_geometry(self.dim, kmax)
-        n_qblk = math.ceil(NQ / qpb)
-        if n_cus is None:
-            n_cus = self._n_cus()
-        n_rblk = max(1, min(math.ceil(n / (TILE_ROWS * self.FILTER_MIN_TILES)),
-                            max(1, round(n_cus / n_qblk))))
-        ncand = n_rblk * lists * kmax
-        cs = torch.empty(NQ, ncand, device=dev)
-        ci = torch.empty(NQ, ncand, dtype=torch.int32, device=dev)
-        st = stream_handle(dev)
-
-        def one_pass(thr, stride):
-            scan(self.rows, n, mask.words, mask.tiles, mask.n_live, q_unit, kmax, n_rblk, cs, ci,
-                 thr, stride, self.scan_xcd, gate)
-            h.topk_merge(cs.data_ptr(), ci.data_ptr(), NQ, ncand, kmax, k, out_s.data_ptr(),
-                         out_i.data_ptr(), 0, 0, st, 0 if gate is None else gate.data_ptr())
-
-        thr = None
-        if self.filter_seed:
-            one_pass(None, self.FILTER_SEED_STRIDE)
-            kth = out_s[:, k - 1].contiguous()
-            thr = torch.nextafter(kth, torch.full_like(kth, -math.inf))
-        one_pass(thr, 1)
-        if fp8:
-            out_s.mul_(1.0 / (FP8_SCALE * FP8_SCALE))   # (-inf stays -inf)
-        return out_s, out_i
+    def _search_group_chunk_large_k(self, q8, k: int, groups: MaskGroups, ch: dict, n_cus,
+                                    seed: bool = True):
+        """The masked large-k search under a mask per query, over one chunk's queries (``q8``:
+        their e4m3 bytes, quantised once per search by _search_grouped): the grouped e4m3 list
+        scan (index_filter_group_fp8.hip) and the grouped emitting scan
+        (index_emit_group_fp8.hip) over the union's live-tile list.  Returns None when a query's
+        candidates overflow LARGE_K_CAP (the flag is read once per chunk); the caller then
+        answers the chunk's groups one mask at a time."""
+        scan, emit = self._masked_kernels(True)
+        return self._masked_large_k(
+            scan, emit, groups.visible, (ch["mask8"], ch["qgroup"], ch["tiles"], ch["n_live"]),
+            q8, k, n_cus, seed=seed)
 
     def _search_scan(self, q_unit, k: int, rows, dtype: str, n_cus):
         """Seeded fused scan + merge over ``rows`` (bf16 slab, or e4m3 bytes for dtype fp8)."""

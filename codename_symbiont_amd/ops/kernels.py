@@ -277,6 +277,102 @@ def filter_tiles(mask_words: torch.Tensor, n_valid: int):
     return tiles, n_live
 
 
+MASK_GROUPS = 8   # masks one grouped scan carries: mask words per tile (index_*_group*.hip)
+FILTER_LARGE_K_DIMS = (384, 768, 1024)   # ... of the masked emitting scan (index_mq_filter.hip)
+# (sets, rsplit) forms it is built for, per width
+_MQ_FILTER_FORMS = {384: ((4, 1), (4, 2)), 768: ((2, 1),), 1024: ((1, 1),)}
+FILTER_FP8_DIMS = (256, 384, 512, 768, 1024)   # ... of the e4m3 forms (index_filter_fp8.hip, ...)
+
+
+def _masked_scan_checks(name, dtype, dims, rows, n_valid, mask, qgroup, tiles, n_live, q, cand_s,
+                        cand_i, gate, scalars):
+    """What the seven masked scans check alike; returns (D, NQ).  ``dtype``: the rows' and the
+    queries' (uint8: e4m3 bytes); ``mask`` / ``qgroup``: mask words and None, or mask8 and the
+    queries' groups; ``scalars``: the family's refusal of its scalar arguments, or None where
+    they are in range.  Every pointer the kernels dereference is bounded here: the slab, the
+    mask and the tile list cover ``n_valid``, ``n_live`` and ``gate`` hold an element."""
+    fp8 = dtype == torch.uint8
+    if fp8 and (rows.dtype != torch.uint8 or q.dtype != torch.uint8):
+        # (a bf16 slab of the same width would be read as twice as many e4m3 rows)
+        raise ValueError(f"{name}: rows and queries are e4m3 bytes (uint8), got "
+                         f"{rows.dtype} / {q.dtype}")
+    _chk(rows, dtype, "rows_u8" if fp8 else "rows", 2)
+    _chk(q, dtype, "q_e4m3" if fp8 else "q_unit", 2)
+    if qgroup is None:
+        _chk(mask, torch.int64, "mask_words", 1)
+    else:
+        _chk(mask, torch.int64, "mask8", 2)
+        _chk(qgroup, torch.int32, "qgroup", 1)
+    _chk(tiles, torch.int32, "tiles", 1)
+    _chk(n_live, torch.int32, "n_live", 1)
+    _chk(cand_s, torch.float32, "cand_s")
+    _chk(cand_i, torch.int32, "cand_i")
+    D, NQ = rows.shape[1], q.shape[0]
+    if D not in dims or q.shape[1] != D:
+        raise ValueError(f"{name}: rows must be {dims} wide, queries alike")
+    if scalars is not None:
+        raise ValueError(f"{name}: {scalars}")
+    what = "mask"
+    if qgroup is not None:
+        what = "mask8"
+        if mask.shape[1] != MASK_GROUPS or not mask.is_contiguous():
+            raise ValueError(f"{name}: mask8 must be contiguous [n_words, {MASK_GROUPS}]")
+        if qgroup.numel() != NQ:
+            raise ValueError(f"{name}: qgroup must hold one group per query")
+    n_tiles = (n_valid + 63) // 64
+    # every tile the list can name lies inside the row slab and has its mask word(s)
+    if (n_valid < 0 or n_live.numel() < 1 or n_tiles * 64 > rows.shape[0]
+            or n_tiles > mask.shape[0] or n_tiles > tiles.numel()):
+        raise ValueError(f"{name}: rows / {what} / tile list shorter than n_valid")
+    if gate is not None:
+        _chk(gate, torch.int32, "gate", 1)
+        if gate.numel() < 1:
+            raise ValueError(f"{name}: gate is one int32 flag")
+    return D, NQ
+
+
+def _list_scan_checks(name, dtype, dims, rows, n_valid, mask, qgroup, tiles, n_live, q, kmax,
+                      n_rblk, cand_s, cand_i, thr_init, stride, gate):
+    """The checks of a masked list scan; returns (D, NQ).  Only the bf16 scans' workspace size
+    asks the extension for anything (``topk_geometry``), after every other check of the
+    operands; an e4m3 scan keeps 2 lists at every width."""
+    ok = kmax in (16, 32) and stride >= 1 and n_rblk >= 1
+    D, NQ = _masked_scan_checks(name, dtype, dims, rows, n_valid, mask, qgroup, tiles, n_live, q,
+                                cand_s, cand_i, gate,
+                                None if ok else "kmax in (16, 32), stride >= 1, n_rblk >= 1")
+    if thr_init is not None:
+        _chk(thr_init, torch.float32, "thr_init", 1)
+        if thr_init.numel() < NQ:
+            raise ValueError(f"{name}: thr_init shorter than the batch")
+    lists = 2 if dtype == torch.uint8 else hip().topk_geometry(D, kmax)[0]
+    need = NQ * n_rblk * lists * kmax
+    if cand_s.numel() < need or cand_i.numel() < need:
+        raise ValueError(f"{name}: candidate workspace too small")
+    return D, NQ
+
+
+def _emit_scan_checks(name, dtype, dims, rows, n_valid, mask, qgroup, tiles, n_live, q, thr,
+                      cand_s, cand_i, cand_n, cap, n_rblk, gate, thr_exact):
+    """The checks of a masked emitting scan; returns (D, NQ).  ``thr_exact``: ``thr`` holds NQ
+    thresholds, no more (the e4m3 scans; the bf16 scan takes a longer ``thr``)."""
+    ok = n_rblk >= 1 and cap >= 1 and n_valid >= 0 and n_live.numel() >= 1
+    D, NQ = _masked_scan_checks(name, dtype, dims, rows, n_valid, mask, qgroup, tiles, n_live, q,
+                                cand_s, cand_i, gate,
+                                None if ok else "n_rblk >= 1, cap >= 1, n_valid >= 0")
+    if thr is None or thr.dtype != torch.float32:
+        raise ValueError(f"{name}: thr is a float32 tensor, one threshold per query")
+    _chk(thr, torch.float32, "thr", 1)
+    _chk(cand_n, torch.int32, "cand_n", 1)
+    if thr.numel() != NQ if thr_exact else thr.numel() < NQ:
+        raise ValueError(f"{name}: one threshold per query" if thr_exact
+                         else f"{name}: thr shorter than the batch")
+    if cand_n.numel() < NQ:
+        raise ValueError(f"{name}: cand_n shorter than the batch")
+    if cand_s.numel() < NQ * cap or cand_i.numel() < NQ * cap:
+        raise ValueError(f"{name}: candidate workspace too small")
+    return D, NQ
+
+
 def index_scan_filter(rows: torch.Tensor, n_valid: int, mask_words: torch.Tensor,
                       tiles: torch.Tensor, n_live: torch.Tensor, q_unit: torch.Tensor, kmax: int,
                       n_rblk: int, cand_s: torch.Tensor, cand_i: torch.Tensor,
@@ -287,40 +383,13 @@ def index_scan_filter(rows: torch.Tensor, n_valid: int, mask_words: torch.Tensor
     ``filter_tiles(mask_words, n_valid)``; ``stride`` walks every stride-th live tile of each
     workgroup's slice only (a seed pass).  ``gate`` (int32 device flag): the scan runs only if
     it is non-zero, and leaves the candidates untouched otherwise."""
-    _chk(rows, torch.bfloat16, "rows", 2)
-    _chk(q_unit, torch.bfloat16, "q_unit", 2)
-    _chk(mask_words, torch.int64, "mask_words", 1)
-    _chk(tiles, torch.int32, "tiles", 1)
-    _chk(n_live, torch.int32, "n_live", 1)
-    _chk(cand_s, torch.float32, "cand_s")
-    _chk(cand_i, torch.int32, "cand_i")
-    D = rows.shape[1]
-    NQ = q_unit.shape[0]
     n_valid, n_rblk, stride = int(n_valid), int(n_rblk), int(stride)
-    if D not in FILTER_DIMS or q_unit.shape[1] != D:
-        raise ValueError(f"index_scan_filter: rows must be {FILTER_DIMS} wide, queries alike")
-    if kmax not in (16, 32) or stride < 1 or n_rblk < 1:
-        raise ValueError("index_scan_filter: kmax in (16, 32), stride >= 1, n_rblk >= 1")
-    n_tiles = (n_valid + 63) // 64
-    # every tile the list can name lies inside the row slab and has a mask word
-    if n_tiles * 64 > rows.shape[0] or n_tiles > mask_words.numel() or n_tiles > tiles.numel():
-        raise ValueError("index_scan_filter: rows / mask / tile list shorter than n_valid")
-    lists, _ = hip().topk_geometry(D, kmax)
-    need = NQ * n_rblk * lists * kmax
-    if cand_s.numel() < need or cand_i.numel() < need:
-        raise ValueError("index_scan_filter: candidate workspace too small")
-    if thr_init is not None:
-        _chk(thr_init, torch.float32, "thr_init", 1)
-        if thr_init.numel() < NQ:
-            raise ValueError("index_scan_filter: thr_init shorter than the batch")
-    if gate is not None:
-        _chk(gate, torch.int32, "gate", 1)
+    D, NQ = _list_scan_checks("index_scan_filter", torch.bfloat16, FILTER_DIMS, rows, n_valid,
+                              mask_words, None, tiles, n_live, q_unit, kmax, n_rblk, cand_s,
+                              cand_i, thr_init, stride, gate)
     hip().index_scan_filter(_ptr(rows), n_valid, D, _ptr(tiles), _ptr(n_live), _ptr(mask_words),
                             stride, n_rblk, _ptr(q_unit), NQ, kmax, _ptr(cand_s), _ptr(cand_i),
                             stream_handle(rows.device), _ptr(thr_init), xcd, _ptr(gate))
-
-
-MASK_GROUPS = 8   # mask words per tile of the grouped masked scan (index_filter_group.hip)
 
 
 def index_scan_filter_group(rows: torch.Tensor, n_valid: int, mask8: torch.Tensor,
@@ -334,49 +403,14 @@ def index_scan_filter_group(rows: torch.Tensor, n_valid: int, mask8: torch.Tenso
     int32 [NQ] names each query's group (its low three bits are used).  ``tiles`` / ``n_live``
     are ``filter_tiles`` of the OR of the eight slots.  Query q's candidates are those of
     ``index_scan_filter`` under slot ``qgroup[q]``'s words, scored bit for bit alike."""
-    _chk(rows, torch.bfloat16, "rows", 2)
-    _chk(q_unit, torch.bfloat16, "q_unit", 2)
-    _chk(mask8, torch.int64, "mask8", 2)
-    _chk(qgroup, torch.int32, "qgroup", 1)
-    _chk(tiles, torch.int32, "tiles", 1)
-    _chk(n_live, torch.int32, "n_live", 1)
-    _chk(cand_s, torch.float32, "cand_s")
-    _chk(cand_i, torch.int32, "cand_i")
-    D = rows.shape[1]
-    NQ = q_unit.shape[0]
     n_valid, n_rblk, stride = int(n_valid), int(n_rblk), int(stride)
-    if D not in FILTER_DIMS or q_unit.shape[1] != D:
-        raise ValueError(f"index_scan_filter_group: rows must be {FILTER_DIMS} wide, queries alike")
-    if kmax not in (16, 32) or stride < 1 or n_rblk < 1:
-        raise ValueError("index_scan_filter_group: kmax in (16, 32), stride >= 1, n_rblk >= 1")
-    if mask8.shape[1] != MASK_GROUPS or not mask8.is_contiguous():
-        raise ValueError("index_scan_filter_group: mask8 must be contiguous "
-                         f"[n_words, {MASK_GROUPS}]")
-    if qgroup.numel() != NQ:
-        raise ValueError("index_scan_filter_group: qgroup must hold one group per query")
-    n_tiles = (n_valid + 63) // 64
-    # every tile the list can name lies inside the row slab and has its eight mask words
-    if n_tiles * 64 > rows.shape[0] or n_tiles > mask8.shape[0] or n_tiles > tiles.numel():
-        raise ValueError("index_scan_filter_group: rows / mask8 / tile list shorter than n_valid")
-    lists, _ = hip().topk_geometry(D, kmax)
-    need = NQ * n_rblk * lists * kmax
-    if cand_s.numel() < need or cand_i.numel() < need:
-        raise ValueError("index_scan_filter_group: candidate workspace too small")
-    if thr_init is not None:
-        _chk(thr_init, torch.float32, "thr_init", 1)
-        if thr_init.numel() < NQ:
-            raise ValueError("index_scan_filter_group: thr_init shorter than the batch")
-    if gate is not None:
-        _chk(gate, torch.int32, "gate", 1)
+    D, NQ = _list_scan_checks("index_scan_filter_group", torch.bfloat16, FILTER_DIMS, rows,
+                              n_valid, mask8, qgroup, tiles, n_live, q_unit, kmax, n_rblk, cand_s,
+                              cand_i, thr_init, stride, gate)
     hip().index_scan_filter_group(_ptr(rows), n_valid, D, _ptr(tiles), _ptr(n_live), _ptr(mask8),
                                   _ptr(qgroup), stride, n_rblk, _ptr(q_unit), NQ, kmax,
                                   _ptr(cand_s), _ptr(cand_i), stream_handle(rows.device),
                                   _ptr(thr_init), xcd, _ptr(gate))
-
-
-FILTER_LARGE_K_DIMS = (384, 768, 1024)   # ... of the masked emitting scan (index_mq_filter.hip)
-# (sets, rsplit) forms it is built for, per width
-_MQ_FILTER_FORMS = {384: ((4, 1), (4, 2)), 768: ((2, 1),), 1024: ((1, 1),)}
 
 
 def index_scan_mq_filter(rows: torch.Tensor, n_valid: int, mask_words: torch.Tensor,
@@ -394,43 +428,17 @@ def index_scan_mq_filter(rows: torch.Tensor, n_valid: int, mask_words: torch.Ten
     grid is ``n_rblk`` row slots per query block, sharing the live tiles evenly.  ``zero_cnt``
     False appends to ``cand_n``.  ``gate`` (int32 device flag): scan and zeroing run only if it
     is non-zero, and leave every buffer untouched otherwise."""
-    _chk(rows, torch.bfloat16, "rows", 2)
-    _chk(q_unit, torch.bfloat16, "q_unit", 2)
-    _chk(mask_words, torch.int64, "mask_words", 1)
-    _chk(tiles, torch.int32, "tiles", 1)
-    _chk(n_live, torch.int32, "n_live", 1)
-    _chk(thr, torch.float32, "thr", 1)
-    _chk(cand_s, torch.float32, "cand_s")
-    _chk(cand_i, torch.int32, "cand_i")
-    _chk(cand_n, torch.int32, "cand_n", 1)
-    D = rows.shape[1]
-    NQ = q_unit.shape[0]
     n_valid, n_rblk, cap = int(n_valid), int(n_rblk), int(cap)
-    if D not in FILTER_LARGE_K_DIMS or q_unit.shape[1] != D:
-        raise ValueError(f"index_scan_mq_filter: rows must be {FILTER_LARGE_K_DIMS} wide, "
-                         "queries alike")
+    D, NQ = _emit_scan_checks("index_scan_mq_filter", torch.bfloat16, FILTER_LARGE_K_DIMS, rows,
+                              n_valid, mask_words, None, tiles, n_live, q_unit, thr, cand_s,
+                              cand_i, cand_n, cap, n_rblk, gate, thr_exact=False)
     if (int(sets), int(rsplit)) not in _MQ_FILTER_FORMS[D]:
         raise ValueError(f"index_scan_mq_filter: (sets, rsplit) at D = {D} is one of "
                          f"{_MQ_FILTER_FORMS[D]}")
-    if n_rblk < 1 or cap < 1 or n_valid < 0 or n_live.numel() < 1:
-        raise ValueError("index_scan_mq_filter: n_rblk >= 1, cap >= 1, n_valid >= 0")
-    n_tiles = (n_valid + 63) // 64
-    # every tile the list can name lies inside the row slab and has a mask word
-    if n_tiles * 64 > rows.shape[0] or n_tiles > mask_words.numel() or n_tiles > tiles.numel():
-        raise ValueError("index_scan_mq_filter: rows / mask / tile list shorter than n_valid")
-    if thr.numel() < NQ or cand_n.numel() < NQ:
-        raise ValueError("index_scan_mq_filter: thr / cand_n shorter than the batch")
-    if cand_s.numel() < NQ * cap or cand_i.numel() < NQ * cap:
-        raise ValueError("index_scan_mq_filter: candidate workspace too small")
-    if gate is not None:
-        _chk(gate, torch.int32, "gate", 1)
     hip().index_scan_mq_filter(_ptr(rows), n_valid, _ptr(tiles), _ptr(n_live), _ptr(mask_words),
                                n_rblk, _ptr(q_unit), NQ, _ptr(thr), _ptr(cand_s), _ptr(cand_i),
                                _ptr(cand_n), cap, xcd, stream_handle(rows.device), int(sets),
                                int(rsplit), _ptr(gate), bool(zero_cnt), D)
-
-
-FILTER_FP8_DIMS = (256, 384, 512, 768, 1024)   # ... of its e4m3 form (index_filter_fp8.hip)
 
 
 def index_scan_filter_fp8(rows_u8: torch.Tensor, n_valid: int, mask_words: torch.Tensor,
@@ -442,38 +450,10 @@ def index_scan_filter_fp8(rows_u8: torch.Tensor, n_valid: int, mask_words: torch
     candidates [NQ][n_rblk][2][kmax] of the allowed rows below ``n_valid``, for ``topk_merge``.
     Scores are raw accumulators (FP8_SCALE**2 * cosine) and ``thr_init`` is in the same units.
     ``tiles`` / ``n_live`` / ``stride`` / ``gate`` as in ``index_scan_filter``."""
-    if rows_u8.dtype != torch.uint8 or q_e4m3.dtype != torch.uint8:
-        # (a bf16 slab of the same width would be read as twice as many e4m3 rows)
-        raise ValueError("index_scan_filter_fp8: rows and queries are e4m3 bytes (uint8), got "
-                         f"{rows_u8.dtype} / {q_e4m3.dtype}")
-    _chk(rows_u8, torch.uint8, "rows_u8", 2)
-    _chk(q_e4m3, torch.uint8, "q_e4m3", 2)
-    _chk(mask_words, torch.int64, "mask_words", 1)
-    _chk(tiles, torch.int32, "tiles", 1)
-    _chk(n_live, torch.int32, "n_live", 1)
-    _chk(cand_s, torch.float32, "cand_s")
-    _chk(cand_i, torch.int32, "cand_i")
-    D = rows_u8.shape[1]
-    NQ = q_e4m3.shape[0]
     n_valid, n_rblk, stride = int(n_valid), int(n_rblk), int(stride)
-    if D not in FILTER_FP8_DIMS or q_e4m3.shape[1] != D:
-        raise ValueError(f"index_scan_filter_fp8: rows must be {FILTER_FP8_DIMS} wide, queries alike")
-    if kmax not in (16, 32) or stride < 1 or n_rblk < 1:
-        raise ValueError("index_scan_filter_fp8: kmax in (16, 32), stride >= 1, n_rblk >= 1")
-    n_tiles = (n_valid + 63) // 64
-    # every tile the list can name lies inside the row slab and has a mask word
-    if (n_valid < 0 or n_tiles * 64 > rows_u8.shape[0] or n_tiles > mask_words.numel()
-            or n_tiles > tiles.numel()):
-        raise ValueError("index_scan_filter_fp8: rows / mask / tile list shorter than n_valid")
-    need = NQ * n_rblk * 2 * kmax
-    if cand_s.numel() < need or cand_i.numel() < need:
-        raise ValueError("index_scan_filter_fp8: candidate workspace too small")
-    if thr_init is not None:
-        _chk(thr_init, torch.float32, "thr_init", 1)
-        if thr_init.numel() < NQ:
-            raise ValueError("index_scan_filter_fp8: thr_init shorter than the batch")
-    if gate is not None:
-        _chk(gate, torch.int32, "gate", 1)
+    D, NQ = _list_scan_checks("index_scan_filter_fp8", torch.uint8, FILTER_FP8_DIMS, rows_u8,
+                              n_valid, mask_words, None, tiles, n_live, q_e4m3, kmax, n_rblk,
+                              cand_s, cand_i, thr_init, stride, gate)
     hip().index_scan_filter_fp8(_ptr(rows_u8), n_valid, D, _ptr(tiles), _ptr(n_live),
                                 _ptr(mask_words), stride, n_rblk, _ptr(q_e4m3), NQ, kmax,
                                 _ptr(cand_s), _ptr(cand_i), stream_handle(rows_u8.device),
@@ -491,48 +471,10 @@ def index_scan_filter_group_fp8(rows_u8: torch.Tensor, n_valid: int, mask8: torc
     ``n_live`` ``filter_tiles`` of the OR of the eight slots.  Query q's candidates
     [NQ][n_rblk][2][kmax] are those of ``index_scan_filter_fp8`` under slot ``qgroup[q]``'s
     words, raw accumulators scored bit for bit alike; ``thr_init`` in the same units."""
-    if rows_u8.dtype != torch.uint8 or q_e4m3.dtype != torch.uint8:
-        # (a bf16 slab of the same width would be read as twice as many e4m3 rows)
-        raise ValueError("index_scan_filter_group_fp8: rows and queries are e4m3 bytes (uint8), "
-                         f"got {rows_u8.dtype} / {q_e4m3.dtype}")
-    _chk(rows_u8, torch.uint8, "rows_u8", 2)
-    _chk(q_e4m3, torch.uint8, "q_e4m3", 2)
-    _chk(mask8, torch.int64, "mask8", 2)
-    _chk(qgroup, torch.int32, "qgroup", 1)
-    _chk(tiles, torch.int32, "tiles", 1)
-    _chk(n_live, torch.int32, "n_live", 1)
-    _chk(cand_s, torch.float32, "cand_s")
-    _chk(cand_i, torch.int32, "cand_i")
-    D = rows_u8.shape[1]
-    NQ = q_e4m3.shape[0]
     n_valid, n_rblk, stride = int(n_valid), int(n_rblk), int(stride)
-    if D not in FILTER_FP8_DIMS or q_e4m3.shape[1] != D:
-        raise ValueError(f"index_scan_filter_group_fp8: rows must be {FILTER_FP8_DIMS} wide, "
-                         "queries alike")
-    if kmax not in (16, 32) or stride < 1 or n_rblk < 1:
-        raise ValueError("index_scan_filter_group_fp8: kmax in (16, 32), stride >= 1, n_rblk >= 1")
-    if mask8.shape[1] != MASK_GROUPS or not mask8.is_contiguous():
-        raise ValueError("index_scan_filter_group_fp8: mask8 must be contiguous "
-                         f"[n_words, {MASK_GROUPS}]")
-    if qgroup.numel() != NQ:
-        raise ValueError("index_scan_filter_group_fp8: qgroup must hold one group per query")
-    n_tiles = (n_valid + 63) // 64
-    # every tile the list can name lies inside the row slab and has its eight mask words
-    if (n_valid < 0 or n_tiles * 64 > rows_u8.shape[0] or n_tiles > mask8.shape[0]
-            or n_tiles > tiles.numel() or n_live.numel() < 1):
-        raise ValueError("index_scan_filter_group_fp8: rows / mask8 / tile list shorter than "
-                         "n_valid")
-    need = NQ * n_rblk * 2 * kmax
-    if cand_s.numel() < need or cand_i.numel() < need:
-        raise ValueError("index_scan_filter_group_fp8: candidate workspace too small")
-    if thr_init is not None:
-        _chk(thr_init, torch.float32, "thr_init", 1)
-        if thr_init.numel() < NQ:
-            raise ValueError("index_scan_filter_group_fp8: thr_init shorter than the batch")
-    if gate is not None:
-        _chk(gate, torch.int32, "gate", 1)
-        if gate.numel() < 1:
-            raise ValueError("index_scan_filter_group_fp8: gate is one int32 flag")
+    D, NQ = _list_scan_checks("index_scan_filter_group_fp8", torch.uint8, FILTER_FP8_DIMS,
+                              rows_u8, n_valid, mask8, qgroup, tiles, n_live, q_e4m3, kmax,
+                              n_rblk, cand_s, cand_i, thr_init, stride, gate)
     hip().index_scan_filter_group_fp8(_ptr(rows_u8), n_valid, D, _ptr(tiles), _ptr(n_live),
                                       _ptr(mask8), _ptr(qgroup), stride, n_rblk, _ptr(q_e4m3), NQ,
                                       kmax, _ptr(cand_s), _ptr(cand_i),
@@ -554,40 +496,10 @@ def index_scan_emit_fp8(rows_u8: torch.Tensor, n_valid: int, mask_words: torch.T
     queries, sharing the live tiles evenly.  ``zero_cnt`` False appends to ``cand_n``.  ``gate``
     (int32 device flag): scan and zeroing run only if it is non-zero, and leave every buffer
     untouched otherwise."""
-    if rows_u8.dtype != torch.uint8 or q_e4m3.dtype != torch.uint8:
-        # (a bf16 slab of the same width would be read as twice as many e4m3 rows)
-        raise ValueError("index_scan_emit_fp8: rows and queries are e4m3 bytes (uint8), got "
-                         f"{rows_u8.dtype} / {q_e4m3.dtype}")
-    _chk(rows_u8, torch.uint8, "rows_u8", 2)
-    _chk(q_e4m3, torch.uint8, "q_e4m3", 2)
-    _chk(mask_words, torch.int64, "mask_words", 1)
-    _chk(tiles, torch.int32, "tiles", 1)
-    _chk(n_live, torch.int32, "n_live", 1)
-    if thr is None or thr.dtype != torch.float32:
-        raise ValueError("index_scan_emit_fp8: thr is a float32 tensor, one threshold per query")
-    _chk(thr, torch.float32, "thr", 1)
-    _chk(cand_s, torch.float32, "cand_s")
-    _chk(cand_i, torch.int32, "cand_i")
-    _chk(cand_n, torch.int32, "cand_n", 1)
-    D = rows_u8.shape[1]
-    NQ = q_e4m3.shape[0]
     n_valid, n_rblk, cap = int(n_valid), int(n_rblk), int(cap)
-    if D not in FILTER_FP8_DIMS or q_e4m3.shape[1] != D:
-        raise ValueError(f"index_scan_emit_fp8: rows must be {FILTER_FP8_DIMS} wide, queries alike")
-    if n_rblk < 1 or cap < 1 or n_valid < 0 or n_live.numel() < 1:
-        raise ValueError("index_scan_emit_fp8: n_rblk >= 1, cap >= 1, n_valid >= 0")
-    n_tiles = (n_valid + 63) // 64
-    # every tile the list can name lies inside the row slab and has a mask word
-    if n_tiles * 64 > rows_u8.shape[0] or n_tiles > mask_words.numel() or n_tiles > tiles.numel():
-        raise ValueError("index_scan_emit_fp8: rows / mask / tile list shorter than n_valid")
-    if thr.numel() != NQ:
-        raise ValueError("index_scan_emit_fp8: one threshold per query")
-    if cand_n.numel() < NQ:
-        raise ValueError("index_scan_emit_fp8: cand_n shorter than the batch")
-    if cand_s.numel() < NQ * cap or cand_i.numel() < NQ * cap:
-        raise ValueError("index_scan_emit_fp8: candidate workspace too small")
-    if gate is not None:
-        _chk(gate, torch.int32, "gate", 1)
+    D, NQ = _emit_scan_checks("index_scan_emit_fp8", torch.uint8, FILTER_FP8_DIMS, rows_u8,
+                              n_valid, mask_words, None, tiles, n_live, q_e4m3, thr, cand_s,
+                              cand_i, cand_n, cap, n_rblk, gate, thr_exact=True)
     hip().index_scan_emit_fp8(_ptr(rows_u8), n_valid, D, _ptr(tiles), _ptr(n_live),
                               _ptr(mask_words), n_rblk, _ptr(q_e4m3), NQ, _ptr(thr),
                               _ptr(cand_s), _ptr(cand_i), _ptr(cand_n), cap,
@@ -607,51 +519,10 @@ def index_scan_emit_group_fp8(rows_u8: torch.Tensor, n_valid: int, mask8: torch.
     ``n_valid`` whose raw score, bit for bit the list scans', lies above ``thr[q]``.
     ``cand_s`` / ``cand_i`` [NQ, cap], ``cand_n`` [NQ] (may exceed ``cap``; nothing is written at
     or past it), ``zero_cnt`` and ``gate`` as there."""
-    if rows_u8.dtype != torch.uint8 or q_e4m3.dtype != torch.uint8:
-        # (a bf16 slab of the same width would be read as twice as many e4m3 rows)
-        raise ValueError("index_scan_emit_group_fp8: rows and queries are e4m3 bytes (uint8), "
-                         f"got {rows_u8.dtype} / {q_e4m3.dtype}")
-    _chk(rows_u8, torch.uint8, "rows_u8", 2)
-    _chk(q_e4m3, torch.uint8, "q_e4m3", 2)
-    _chk(mask8, torch.int64, "mask8", 2)
-    _chk(qgroup, torch.int32, "qgroup", 1)
-    _chk(tiles, torch.int32, "tiles", 1)
-    _chk(n_live, torch.int32, "n_live", 1)
-    if thr is None or thr.dtype != torch.float32:
-        raise ValueError("index_scan_emit_group_fp8: thr is a float32 tensor, one threshold per "
-                         "query")
-    _chk(thr, torch.float32, "thr", 1)
-    _chk(cand_s, torch.float32, "cand_s")
-    _chk(cand_i, torch.int32, "cand_i")
-    _chk(cand_n, torch.int32, "cand_n", 1)
-    D = rows_u8.shape[1]
-    NQ = q_e4m3.shape[0]
     n_valid, n_rblk, cap = int(n_valid), int(n_rblk), int(cap)
-    if D not in FILTER_FP8_DIMS or q_e4m3.shape[1] != D:
-        raise ValueError(f"index_scan_emit_group_fp8: rows must be {FILTER_FP8_DIMS} wide, "
-                         "queries alike")
-    if n_rblk < 1 or cap < 1 or n_valid < 0 or n_live.numel() < 1:
-        raise ValueError("index_scan_emit_group_fp8: n_rblk >= 1, cap >= 1, n_valid >= 0")
-    if mask8.shape[1] != MASK_GROUPS or not mask8.is_contiguous():
-        raise ValueError("index_scan_emit_group_fp8: mask8 must be contiguous "
-                         f"[n_words, {MASK_GROUPS}]")
-    if qgroup.numel() != NQ:
-        raise ValueError("index_scan_emit_group_fp8: qgroup must hold one group per query")
-    n_tiles = (n_valid + 63) // 64
-    # every tile the list can name lies inside the row slab and has its eight mask words
-    if n_tiles * 64 > rows_u8.shape[0] or n_tiles > mask8.shape[0] or n_tiles > tiles.numel():
-        raise ValueError("index_scan_emit_group_fp8: rows / mask8 / tile list shorter than "
-                         "n_valid")
-    if thr.numel() != NQ:
-        raise ValueError("index_scan_emit_group_fp8: one threshold per query")
-    if cand_n.numel() < NQ:
-        raise ValueError("index_scan_emit_group_fp8: cand_n shorter than the batch")
-    if cand_s.numel() < NQ * cap or cand_i.numel() < NQ * cap:
-        raise ValueError("index_scan_emit_group_fp8: candidate workspace too small")
-    if gate is not None:
-        _chk(gate, torch.int32, "gate", 1)
-        if gate.numel() < 1:
-            raise ValueError("index_scan_emit_group_fp8: gate is one int32 flag")
+    D, NQ = _emit_scan_checks("index_scan_emit_group_fp8", torch.uint8, FILTER_FP8_DIMS, rows_u8,
+                              n_valid, mask8, qgroup, tiles, n_live, q_e4m3, thr, cand_s, cand_i,
+                              cand_n, cap, n_rblk, gate, thr_exact=True)
     hip().index_scan_emit_group_fp8(_ptr(rows_u8), n_valid, D, _ptr(tiles), _ptr(n_live),
                                     _ptr(mask8), _ptr(qgroup), n_rblk, _ptr(q_e4m3), NQ,
                                     _ptr(thr), _ptr(cand_s), _ptr(cand_i), _ptr(cand_n), cap,
