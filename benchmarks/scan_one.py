@@ -38,9 +38,10 @@ def main() -> None:
                          "centroid test off), e.g. 0:1,0:0")
     ap.add_argument("--reserve-sweep", default="",
                     help="--tier mx4 on the stream image: time the scan's forms in one process, "
-                         "interleaved: comma list of wide:R:depth (wide 0 = the thin form, 1 = "
-                         "the CU-granular one; R = CUs left free, which sizes the block grid; "
-                         "depth 0 = the kernel's default), e.g. 0:0:0,1:0:0,1:64:0,1:64:4")
+                         "interleaved: comma list of wide:R:depth[:nt] (wide 0 = the thin form, 1 "
+                         "= the CU-granular one; R = CUs left free, which sizes the block grid; "
+                         "depth 0 = the kernel's default; nt 1 = the non-temporal row stream, "
+                         "default 0), e.g. 0:0:0,1:0:0,1:64:0,1:64:4,1:96:0:1")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--thr-add", type=float, default=0.0,
                     help="added to the scan's thresholds (e.g. 10: no row emits -- kernel-only timing)")
@@ -127,17 +128,19 @@ def main() -> None:
         if a.tier != "mx4" or shard.img_mx4 is None:
             raise SystemExit("--reserve-sweep times the MX-fp4 stream scan (--tier mx4)")
         sweep = [tuple(int(x) for x in f.split(":")) for f in a.reserve_sweep.split(",")]
+        sweep = [f + (0,) * (4 - len(f)) for f in sweep]   # (nt defaults to 0)
+        from codename_symbiont_amd.ops import kernels as K
         n_cus = shard._n_cus()
         kw = shard._cent_args(m4)
 
-        def scan_form(wide, R, depth):
+        def scan_form(wide, R, depth, nt):
             _, rpb, nrb = shard._i8_geometry(n, a.nq, n_cus, R)
             P["cnt"].zero_()
-            h.index_scan_stream(shard.img_mx4.data_ptr(), n, shard.img_mx4.shape[0] * STREAM_SUB,
+            K.index_scan_stream(shard.img_mx4.data_ptr(), n, shard.img_mx4.shape[0] * STREAM_SUB,
                                 rpb, nrb, m4["q4"].data_ptr(), m4["qs4"].data_ptr(), a.nq,
                                 m4["thr4"].data_ptr(), P["cs"].data_ptr(), P["ci"].data_ptr(),
                                 P["cnt"].data_ptr(), P["cap"], 1, st, dim=a.dim, form=1,
-                                wide=wide, depth=depth, **kw)
+                                wide=wide, depth=depth, nt=nt, **kw)
             return rpb, nrb
 
         times = {f: [] for f in sweep}
@@ -154,7 +157,7 @@ def main() -> None:
         for f, ts in times.items():
             ms = sorted(ts)[len(ts) // 2]
             print(json.dumps({"bench": "scan_one", "kernel": "stream-mx4", "wide": f[0],
-                              "reserve": f[1], "depth": f[2], "rows": n, "nq": a.nq, "dim": a.dim,
+                              "reserve": f[1], "depth": f[2], "nt": f[3], "rows": n, "nq": a.nq, "dim": a.dim,
                               "queries": a.queries, "ms": round(ms, 3),
                               "ms_all": [round(t, 3) for t in ts],
                               "TBps": round(n * nbytes / ms / 1e9, 2), "n_rblk": geo[f][1],

@@ -579,6 +579,21 @@ class HbmIndexShard:
         # wave at dim 384 (0 = the kernel's 3; 4, 5; SYMB_SCAN_DEPTH)
         self.scan_reserve = int(os.environ.get("SYMB_SCAN_RESERVE", "") or self.SCAN_RESERVE)
         self.scan_depth = int(os.environ.get("SYMB_SCAN_DEPTH", "") or 0)
+        # scan_nt: the fp4 stream scan at dim 384 loads its rows non-temporally (index_stream.hip
+        # NT_; SYMB_SCAN_NT for A/B runs) -- the one form whose sub-tiles are read once each
+        self.scan_nt = int(os.environ.get("SYMB_SCAN_NT", "") or self.SCAN_NT)
+        # prune_fused_finish: the pruned search ends in one launch (prune_finish.hip: re-score,
+        # top-k, tier word) instead of rescore_bf16 + topk_select_counted + a host copy.
+        # route_at_begin: a split-phase search enqueues the candidate prefill and the bf16 scan of
+        # the routed blocks in its begin half (they read nothing the stream scan writes).
+        # Both shorten the compute stream's tail between two scans and both are OFF by default:
+        # the headline step is paced by the encoder stream, and with them on it measured the same
+        # within the run-to-run spread (profiles/r17_step/README.md); SYMB_PRUNE_FINISH=1 /
+        # SYMB_ROUTE_AT_BEGIN=1 switch them on for A/B runs.
+        self.prune_fused_finish = os.environ.get("SYMB_PRUNE_FINISH", "0") not in ("", "0")
+        self.route_at_begin = os.environ.get("SYMB_ROUTE_AT_BEGIN", "0") not in ("", "0")
+        self._tier_words = None   # pinned ring of tier words (prune_finish writes them)
+        self._tier_slot = 0
         self.scan_mq = True
         self.mq_min_nq = 256   # smallest batch for the emitting kernel (< 512: a 256-query form)
         # smallest batch for the int8-pruned search: its scan costs about the same for 1..256
@@ -2361,6 +2376,7 @@ class HbmIndexShard:
             plan, ts = self._tile_sample_plan(n, ts, want_idx=False), ts - 1
         if plan is None:
             return None
+        two_phase = split
         split = split and n_cus is None
         if n_cus is None:
             n_cus = self._n_cus()
@@ -2486,7 +2502,68 @@ class HbmIndexShard:
                 h.mx4_centroids(q4.data_ptr(), qs4.data_ptr(), NQ, self.dim, c4.data_ptr(),
                                 cqs.data_ptr(), cR.data_ptr(), st)
                 ctx["mx4"].update(c4=c4, cqs=cqs, cR=cR)
+        if two_phase and self.route_at_begin:
+            # What the full-shard half does not need the stream scan for runs here, under the
+            # previous search's scan: the candidate buffers, the partial sub-tile's prefill (first:
+            # it STORES the counters) and the bf16 scan of the routed blocks.  They read the bf16
+            # rows below n, T and the route's list -- nothing a later append (rows at or past n),
+            # a tombstone (a zeroed row is re-scored as such by the finish, and search_end checks
+            # the result against the live mask) or the stream scan writes; a re-calibration
+            # between the halves drops these candidates with the rest (the gen check), and a
+            # compaction is ordered against running searches by the caller as any write is.
+            cs, ci = self._cand_buffers(NQ)
+            n_scan = self._cand_prefill(h, st, NQ, n, ci, cnt_f)
+            self._route_scan(h, st, q_unit, n_scan, n_cus, T, blk, geo[1], cs, ci, cnt_f)
+            ctx["cand"] = (cs, ci, n_scan)
         return ctx
+
+    def _cand_buffers(self, NQ: int):
+        """(scores, ids) of the pruned search's candidates: [NQ, PRUNE_CAP] each."""
+        return (torch.empty(NQ, self.PRUNE_CAP, device=self.device),
+                torch.empty(NQ, self.PRUNE_CAP, dtype=torch.int32, device=self.device))
+
+    def _cand_prefill(self, h, st, NQ: int, n: int, ci, cnt) -> int:
+        """-> n_scan, the rows the first-pass scans cover.  They stop at the last whole 32-row
+        sub-tile: an append into a partly filled one re-quantises its rows under a new shared
+        int8 scale (and raises E past what this search's margins assumed), and a pipelined
+        caller appends batch i + 1 while batch i's scan runs.  The < 32 rows past the boundary
+        enter every query's candidate list unconditionally (prefill_candidates, which stores the
+        counters: before any scan adds to them) and are re-scored exactly like any candidate."""
+        n_scan = n - n % STREAM_SUB if self.stream else n
+        if n_scan < n:
+            h.prefill_candidates(NQ, n_scan, n - n_scan, ci.data_ptr(), cnt.data_ptr(),
+                                 self.PRUNE_CAP, st)
+        return n_scan
+
+    def _route_scan(self, h, st, q_unit, n_scan: int, n_cus: int, T, blk, rows_per_blk: int,
+                    cs, ci, cnt) -> None:
+        """The bf16 emitting scan of the blocks the route listed, at the exact threshold T, into
+        the candidate buffers (no launch work when none is listed)."""
+        if not self.prune_route:
+            return
+        NQ = q_unit.shape[0]
+        sets, mrs, _, slots = self._mq_slots(NQ, n_cus)
+        h.index_scan_mq(self.rows.data_ptr(), n_scan, TILE_ROWS, slots, q_unit.data_ptr(), NQ,
+                        T.data_ptr(), cs.data_ptr(), ci.data_ptr(), cnt.data_ptr(),
+                        self.PRUNE_CAP, self.scan_xcd, st, sets, 0, mrs, blist=blk.data_ptr(),
+                        list_tiles=rows_per_blk // TILE_ROWS, zero_cnt=False, dim=self.dim)
+
+    def _tier_word(self):
+        """-> (pinned int32 [1] view, its device address) for one search's tier word, from a ring
+        of pinned, device-mapped words the finish kernel stores into; (None, 0) when the pinned
+        memory has no device address (the caller copies the word as before)."""
+        from ..ops._ext import hip
+
+        if self._tier_words is None:
+            w = torch.zeros(64, dtype=torch.int32, pin_memory=True)
+            self._tier_words = (w, int(hip().host_device_ptr(w.data_ptr())))
+        w, base = self._tier_words
+        if not base:
+            return None, 0
+        with self._tier_lock:
+            slot = self._tier_slot
+            self._tier_slot = (slot + 1) % w.numel()
+        return w[slot:slot + 1], base + 4 * slot
 
     # the search workspace's flag slots (_pruned_begin): route "every block dense", the MX-fp4
     # tier's "not viable" flag, the sample's and the final select's overflow flags, and a slot
@@ -2506,6 +2583,8 @@ class HbmIndexShard:
 
     # default of ``scan_reserve`` (profiles/r7_reserve/README.md has the sweep)
     SCAN_RESERVE = 96
+    # default of ``scan_nt`` (profiles/r17_step/README.md has the A/B)
+    SCAN_NT = 1
 
     def _scan_reserve(self, split: bool, n_cus: int, NQ: int) -> int:
         """CUs the stream scans of this search leave whole (``scan_reserve``), 0 outside the one
@@ -2608,21 +2687,19 @@ class HbmIndexShard:
         # 3. int8 scan of the blocks the route kept: emit every row with (q8 . x8) * sx >= thr
         #    (candidate counters and overflow flag: the workspace _pruned_begin cleared)
         ws = ctx["ws"]
-        cs = torch.empty(NQ, cap, device=dev)
-        ci = torch.empty(NQ, cap, dtype=torch.int32, device=dev)
         cnt = ws[NQ:2 * NQ]
+        early = ctx.get("cand")   # (_pruned_begin: prefill and routed blocks already enqueued)
+        if early is None:
+            cs, ci = self._cand_buffers(NQ)
+            n_scan = self._cand_prefill(h, st, NQ, n, ci, cnt)
+        else:
+            cs, ci, n_scan = early
+            cs.record_stream(cur)
+            ci.record_stream(cur)
         ovf = ws[2 * NQ + self.WS_OVF:2 * NQ + self.WS_OVF + 1]
         out_s = torch.empty(NQ, k, device=dev)
         out_i = torch.empty(NQ, k, dtype=torch.int32, device=dev)
         skip = blk[2 + n_rblk:].data_ptr() if self.prune_route else 0
-        # The scans stop at the last whole 32-row sub-tile: an append into a partly filled one
-        # re-quantises its rows under a new shared int8 scale (and raises E past what this
-        # search's margins assumed), and a pipelined caller appends batch i + 1 while batch i's
-        # scan runs.  The < 32 rows past the boundary enter every query's candidate list
-        # unconditionally (prefill_candidates) and are re-scored exactly like any candidate.
-        n_scan = n - n % STREAM_SUB if self.stream else n
-        if n_scan < n:
-            h.prefill_candidates(NQ, n_scan, n - n_scan, ci.data_ptr(), cnt.data_ptr(), cap, st)
         # both tiers are enqueued, gated on the MX-fp4 flag (0: the fp4 tier runs, 1: the int8 /
         # split tier): exactly one runs
         m4 = ctx.get("mx4")
@@ -2651,6 +2728,8 @@ class HbmIndexShard:
                                 gate=gate, gate_want=want, zero_cnt=0)
 
         def tier_mx4():
+            from ..ops import kernels as K
+
             if self.img_mx4 is not None:
                 # (runs: the device counter of searches whose first tier was this scan)
                 runs = 0
@@ -2658,14 +2737,16 @@ class HbmIndexShard:
                     if self._mx4_tot is None:
                         self._mx4_tot = torch.zeros(1, dtype=torch.int32, device=dev)
                     runs = self._mx4_tot.data_ptr()
-                h.index_scan_stream(self.img_mx4.data_ptr(), n_scan,
+                depth = self.scan_depth if self.dim == 384 else 0
+                K.index_scan_stream(self.img_mx4.data_ptr(), n_scan,
                                     self.img_mx4.shape[0] * STREAM_SUB, rows_per_blk, n_rblk,
                                     m4["q4"].data_ptr(), m4["qs4"].data_ptr(), NQ,
                                     m4["thr4"].data_ptr(), cs.data_ptr(), ci.data_ptr(),
                                     cnt.data_ptr(), cap, self.scan_xcd, st, skip=skip,
                                     dim=self.dim, form=1, gate=m4["nv"].data_ptr(), gate_want=0,
-                                    zero_cnt=0, runs=runs, wide=wide,
-                                    depth=self.scan_depth if self.dim == 384 else 0,
+                                    zero_cnt=0, runs=runs, wide=wide, depth=depth,
+                                    nt=int(bool(self.scan_nt)
+                                           and K.scan_stream_nt_ok(self.dim, 1, depth)),
                                     **self._cent_args(m4))
             else:
                 h.index_scan_i8(self.rows_mx4.data_ptr(), self.sc_mx4.data_ptr(), n_scan,
@@ -2687,20 +2768,26 @@ class HbmIndexShard:
         else:
             tier_i8()
             tier_mx4()
-        # 3'. the bf16 emitting scan of the blocks the route listed, at the exact threshold T,
-        #     into the same candidate buffers (no launch work when none is listed)
-        if self.prune_route:
-            sets, mrs, _, slots = self._mq_slots(NQ, n_cus)
-            h.index_scan_mq(self.rows.data_ptr(), n_scan, TILE_ROWS, slots, q_unit.data_ptr(), NQ,
-                            T.data_ptr(), cs.data_ptr(), ci.data_ptr(), cnt.data_ptr(), cap,
-                            self.scan_xcd, st, sets, 0, mrs, blist=blk.data_ptr(),
-                            list_tiles=rows_per_blk // TILE_ROWS, zero_cnt=False, dim=self.dim)
-        # 4. exact bf16 re-score of every candidate, 5. top-k
-        h.rescore_bf16(self.rows.data_ptr(), q_unit.data_ptr(), NQ, self.dim, ci.data_ptr(),
-                       cnt.data_ptr(), cap, cs.data_ptr(), st)
-        h.topk_select_counted(cs.data_ptr(), ci.data_ptr(), cnt.data_ptr(), cap, NQ, kmax, k,
-                              out_s.data_ptr(), out_i.data_ptr(), ovf.data_ptr(), st,
-                              reset_ovf=False)
+        # 3'. the bf16 emitting scan of the blocks the route listed, into the same candidate
+        #     buffers (a split-phase search ran it in its begin half)
+        if early is None:
+            self._route_scan(h, st, q_unit, n_scan, n_cus, T, blk, rows_per_blk, cs, ci, cnt)
+        # 4. exact bf16 re-score of every candidate, 5. top-k -- one launch (prune_finish.hip),
+        #    which also stores the tier word for a later search's hint into a pinned host word
+        flag, host_word = None, 0
+        if self.prune_fused_finish:
+            from ..ops import kernels as K
+
+            if tier is not None and dev.type == "cuda":
+                flag, host_word = self._tier_word()
+            K.prune_finish(self.rows, q_unit, ci, cnt, cs, k, out_s, out_i, ovf,
+                           tier=tier if host_word else None, host_word=host_word)
+        else:
+            h.rescore_bf16(self.rows.data_ptr(), q_unit.data_ptr(), NQ, self.dim, ci.data_ptr(),
+                           cnt.data_ptr(), cap, cs.data_ptr(), st)
+            h.topk_select_counted(cs.data_ptr(), ci.data_ptr(), cnt.data_ptr(), cap, NQ, kmax, k,
+                                  out_s.data_ptr(), out_i.data_ptr(), ovf.data_ptr(), st,
+                                  reset_ovf=False)
         # overflow (some query had more than cap candidates): the exact bf16 scan, seeded with T
         self._scan(n, q_unit, kmax, k, T.contiguous(), n_cus, gate=ovf, out=(out_s, out_i))
         self._mq_last = (cnt, ovf)
@@ -2708,8 +2795,9 @@ class HbmIndexShard:
         self._mx4_last = None if m4 is None else m4["nv"]   # 0: the MX-fp4 tier ran
         self._tier_last = tier   # 0 fp4, 1 int8 / split
         if tier is not None and dev.type == "cuda":
-            flag = torch.empty(1, dtype=torch.int32, pin_memory=True)
-            flag.copy_(tier, non_blocking=True)
+            if flag is None:   # (no fused finish, or no device address for the pinned word)
+                flag = torch.empty(1, dtype=torch.int32, pin_memory=True)
+                flag.copy_(tier, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(cur)
             with self._tier_lock:

@@ -634,3 +634,70 @@ def compact_rows(dead_words: torch.Tensor, tile_dst: torch.Tensor, t0: int, t1: 
                        slab.element_size(), _ptr(stage), _ptr(slab2),
                        0 if slab2 is None else slab2.element_size(), _ptr(stage2), D, n_rows, cap,
                        stream_handle(dev))
+
+
+def scan_stream_nt_ok(dim: int, form: int, depth: int = 0) -> bool:
+    """Does the stream scan (index_stream.hip) have a non-temporal row stream for this form?
+    Only where every sub-tile is read by exactly one wave, once: MX-fp4 (form 1) at width 384,
+    at the kernel's default depth (0, or 3 by its number)."""
+    return int(form) == 1 and int(dim) == 384 and int(depth) in (0, 3)
+
+
+def index_scan_stream(*args, nt: int = 0, **kw) -> None:
+    """``_hip.index_scan_stream`` with the ``nt`` argument checked first: the non-temporal row
+    stream is refused, before the extension is touched, for every form that has none (the int8
+    image, widths 768 / 1024, depths 4 / 5 -- scan_stream_nt_ok).  Every other argument is passed
+    through as the binding takes it (raw pointers, the stream handle)."""
+    nt = int(nt)
+    if nt not in (0, 1):
+        raise ValueError(f"index_scan_stream: nt must be 0 or 1, got {nt}")
+    if nt:
+        dim, form, depth = kw.get("dim", 384), kw.get("form", 0), kw.get("depth", 0)
+        if not scan_stream_nt_ok(dim, form, depth):
+            raise ValueError(f"index_scan_stream: no non-temporal form for dim {dim}, form {form}, "
+                             f"depth {depth} (MX-fp4 at 384, default depth only)")
+    hip().index_scan_stream(*args, nt=nt, **kw)
+
+
+def prune_finish(rows: torch.Tensor, q_unit: torch.Tensor, cand_i: torch.Tensor,
+                 cand_n: torch.Tensor, cand_s: torch.Tensor, k: int, out_s: torch.Tensor,
+                 out_i: torch.Tensor, ovf: torch.Tensor, tier: torch.Tensor | None = None,
+                 host_word: int = 0) -> None:
+    """The pruned search's finish in one launch (prune_finish.hip): every query's first
+    ``min(cand_n[q], cap)`` candidates ``cand_i[q]`` (int32 [NQ, cap], rows of ``rows``) are
+    re-scored exactly against the bf16 ``rows`` into ``cand_s`` (f32 [NQ, cap]) and their top
+    ``k`` (<= 16) goes to ``out_s`` / ``out_i`` ([NQ, k]; missing slots (-inf, -1)).  A count above
+    cap raises ``ovf[0]`` (int32, never cleared here).  ``tier`` (int32 [1] on the device) and
+    ``host_word`` (the device address of a pinned host int32, ``_hip.host_device_ptr``): the
+    kernel copies the one to the other; both or neither."""
+    _chk(rows, torch.bfloat16, "rows", 2)
+    _chk(q_unit, torch.bfloat16, "q_unit", 2)
+    _chk(cand_i, torch.int32, "cand_i", 2)
+    _chk(cand_s, torch.float32, "cand_s", 2)
+    _chk(cand_n, torch.int32, "cand_n", 1)
+    _chk(out_s, torch.float32, "out_s", 2)
+    _chk(out_i, torch.int32, "out_i", 2)
+    _chk(ovf, torch.int32, "ovf", 1)
+    NQ, D = q_unit.shape
+    cap, k = cand_i.shape[1], int(k)
+    if D not in SUPPORTED_H or rows.shape[1] != D or rows.shape[0] < 1:
+        raise ValueError(f"prune_finish: rows {tuple(rows.shape)} / queries {tuple(q_unit.shape)}: "
+                         f"width must be one of {SUPPORTED_H}")
+    if not 0 < k <= 16:
+        raise ValueError(f"prune_finish: k = {k} outside 1 .. 16")
+    if (cand_i.shape != (NQ, cap) or cand_s.shape != (NQ, cap) or cap < 1 or cand_n.numel() < NQ
+            or out_s.shape != (NQ, k) or out_i.shape != (NQ, k) or ovf.numel() < 1):
+        raise ValueError("prune_finish: candidate / output buffers do not match "
+                         f"[{NQ}, cap] / [{NQ}, {k}]")
+    dev = rows.device
+    for name, t in (("q_unit", q_unit), ("cand_i", cand_i), ("cand_n", cand_n), ("cand_s", cand_s),
+                    ("out_s", out_s), ("out_i", out_i), ("ovf", ovf), ("tier", tier)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"prune_finish: {name} on {t.device}, rows on {dev}")
+    if (tier is None) != (not host_word):
+        raise ValueError("prune_finish: tier and host_word come together")
+    if tier is not None:
+        _chk(tier, torch.int32, "tier", 1)
+    hip().prune_finish(_ptr(rows), rows.shape[0], _ptr(q_unit), NQ, D, _ptr(cand_i), _ptr(cand_n),
+                       cap, _ptr(cand_s), 16, k, _ptr(out_s), _ptr(out_i), _ptr(ovf),
+                       stream_handle(dev), tier=_ptr(tier), host_word=int(host_word))

@@ -155,7 +155,7 @@ int symb_index_scan_stream(const void* img, int n_valid, int alloc_rows, int row
                            hipStream_t st, const int* skip, int dim, int form, const int* gate,
                            int gate_want, int zero_cnt, int* runs, const void* cent4,
                            const void* centqs, const float* centR, const float* bounds4, int wide,
-                           int depth);
+                           int depth, int nt);
 int symb_mx4_centroids(const void* Xq, const void* QS, int NQ, int dim, void* C4, void* CS,
                        float* R, hipStream_t st);
 int symb_append_rows(const void* src, int n, int dim, void* rows, int r0, void* img8, float* b8,
@@ -188,6 +188,10 @@ int symb_i8_tile_rows();
 int symb_i8_wgs_per_cu();
 int symb_rescore_bf16(const void* X, const void* Q, int NQ, int dim, const int* cand_i,
                       const int* cand_n, int cap, float* cand_s, hipStream_t st);
+// the pruned search's finish: re-score + top-k + tier word in one launch (prune_finish.hip)
+int symb_prune_finish(const void* X, int n_rows, const void* Q, int NQ, int dim, const int* cand_i,
+                      const int* cand_n, int cap, float* cand_s, int kmax, int k, float* out_s,
+                      int* out_i, int* ovf, const int* tier, int* host_word, hipStream_t st);
 int symb_quant_rows_i8(const void* X, int n, int dim, void* X8, float* sx, float* err, float* xtn,
                        float* bounds, hipStream_t st);
 int symb_prune_qprep(const void* Q, int NQ, int dim, const float* pre_s, const float* tail_s, int k,
@@ -683,13 +687,13 @@ PYBIND11_MODULE(_hip, m) {
                                 uptr cand_n, int cap, int xcd, uptr st, uptr skip, int dim,
                                 int form, uptr gate, int gate_want, int zero_cnt, uptr runs,
                                 uptr cent4, uptr centqs, uptr centR, uptr bounds4, int wide,
-                                int depth) {
+                                int depth, int nt) {
     check(symb_index_scan_stream(P<void>(img), n_valid, alloc_rows, rows_per_blk, n_rblk,
                                  P<void>(Q), P<void>(qsc), NQ, P<const float>(thr),
                                  P<float>(cand_s), P<int>(cand_i), P<int>(cand_n), cap, xcd, S(st),
                                  P<const int>(skip), dim, form, P<const int>(gate), gate_want,
                                  zero_cnt, P<int>(runs), P<void>(cent4), P<void>(centqs),
-                                 P<const float>(centR), P<const float>(bounds4), wide, depth),
+                                 P<const float>(centR), P<const float>(bounds4), wide, depth, nt),
           "index_scan_stream");
   }, py::arg("img"), py::arg("n_valid"), py::arg("alloc_rows"), py::arg("rows_per_blk"),
      py::arg("n_rblk"), py::arg("Q"), py::arg("qsc"), py::arg("NQ"), py::arg("thr"),
@@ -697,7 +701,7 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("stream"), py::arg("skip") = 0, py::arg("dim") = 384, py::arg("form") = 0,
      py::arg("gate") = 0, py::arg("gate_want") = 0, py::arg("zero_cnt") = 1, py::arg("runs") = 0,
      py::arg("cent4") = 0, py::arg("centqs") = 0, py::arg("centR") = 0, py::arg("bounds4") = 0,
-     py::arg("wide") = 0, py::arg("depth") = 0);
+     py::arg("wide") = 0, py::arg("depth") = 0, py::arg("nt") = 0);
   m.def("mx4_centroids", [](uptr Xq, uptr QS, int NQ, int dim, uptr C4, uptr CS, uptr R, uptr st) {
     check(symb_mx4_centroids(P<void>(Xq), P<void>(QS), NQ, dim, P<void>(C4), P<void>(CS),
                              P<float>(R), S(st)),
@@ -794,6 +798,28 @@ PYBIND11_MODULE(_hip, m) {
                             P<const int>(cand_n), cap, P<float>(cand_s), S(st)),
           "rescore_bf16");
   });
+  m.def("prune_finish", [](uptr X, int n_rows, uptr Q, int NQ, int dim, uptr cand_i, uptr cand_n,
+                           int cap, uptr cand_s, int kmax, int k, uptr out_s, uptr out_i, uptr ovf,
+                           uptr st, uptr tier, uptr host_word) {
+    check(symb_prune_finish(P<void>(X), n_rows, P<void>(Q), NQ, dim, P<const int>(cand_i),
+                            P<const int>(cand_n), cap, P<float>(cand_s), kmax, k, P<float>(out_s),
+                            P<int>(out_i), P<int>(ovf), P<const int>(tier), P<int>(host_word),
+                            S(st)),
+          "prune_finish");
+  }, py::arg("X"), py::arg("n_rows"), py::arg("Q"), py::arg("NQ"), py::arg("dim"),
+     py::arg("cand_i"), py::arg("cand_n"), py::arg("cap"), py::arg("cand_s"), py::arg("kmax"),
+     py::arg("k"), py::arg("out_s"), py::arg("out_i"), py::arg("ovf"), py::arg("stream"),
+     py::arg("tier") = 0, py::arg("host_word") = 0);
+  // the device address of a pinned (page-locked) host word, 0 if the memory is not mapped into
+  // the device's address space -- prune_finish's host_word
+  m.def("host_device_ptr", [](uptr host) -> uptr {
+    void* d = nullptr;
+    if (host == 0 || hipHostGetDevicePointer(&d, P<void>(host), 0) != hipSuccess) {
+      (void)hipGetLastError();   // (not sticky: the caller falls back to a copy)
+      return 0;
+    }
+    return reinterpret_cast<uptr>(d);
+  }, py::arg("host"));
   m.def("quant_rows_i8", [](uptr X, int n, int dim, uptr X8, uptr sx, uptr err, uptr xtn, uptr st,
                             uptr bounds) {
     check(symb_quant_rows_i8(P<void>(X), n, dim, P<void>(X8), P<float>(sx), P<float>(err),

@@ -300,50 +300,7 @@ __global__ __launch_bounds__(512, 1) void index_scan_mq_kernel(
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tail prefetches and emissions
 }
 
-// Wave-wide max of a float, valid in lane 63: DPP row shifts fold each 16-lane row, then two row
-// broadcasts fold the rows (max is idempotent, so lanes whose DPP source is out of range simply
-// keep their own value).
-__device__ __forceinline__ float wave_max63(float v) {
-  int x = __float_as_int(v);
-  x = __float_as_int(fmaxf(__int_as_float(x), __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0x111, 0xf, 0xf, false))));
-  x = __float_as_int(fmaxf(__int_as_float(x), __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0x112, 0xf, 0xf, false))));
-  x = __float_as_int(fmaxf(__int_as_float(x), __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0x114, 0xf, 0xf, false))));
-  x = __float_as_int(fmaxf(__int_as_float(x), __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0x118, 0xf, 0xf, false))));
-  x = __float_as_int(fmaxf(__int_as_float(x), __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0x142, 0xa, 0xf, false))));
-  x = __float_as_int(fmaxf(__int_as_float(x), __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0x143, 0xc, 0xf, false))));
-  return __int_as_float(__builtin_amdgcn_readlane(x, 63));
-}
-
-// KMAX rounds of a wave-wide "pop the best head": every lane holds a descending list of L
-// candidates; each round the wave max of the heads (DPP, no LDS), the lowest lane holding it gives
-// up its head (its list shifts by one) and lane r keeps round r's winner.  Replaces the LDS tree
-// of pairwise merges (8 rounds x 2 barriers x a 16-step serial merge per level).
-template <int KMAX, int L>
-__device__ __forceinline__ void wave_pop_topk(float (&tv)[L], int (&ti)[L], int lane, float& rv,
-                                              int& ri) {
-  rv = -INFINITY;
-  ri = -1;
-#pragma unroll
-  for (int r = 0; r < KMAX; ++r) {
-    const float mx = wave_max63(tv[0]);
-    const uint64_t hit = __ballot(tv[0] == mx);
-    const int win = hit ? (int)__builtin_ctzll(hit) : 0;
-    const int id = __builtin_amdgcn_readlane(ti[0], win);
-    if (lane == r) {
-      rv = mx;
-      ri = id;
-    }
-    if (lane == win) {
-#pragma unroll
-      for (int i = 0; i + 1 < L; ++i) {
-        tv[i] = tv[i + 1];
-        ti[i] = ti[i + 1];
-      }
-      tv[L - 1] = -INFINITY;
-      ti[L - 1] = -1;
-    }
-  }
-}
+// (wave_max63 / wave_pop_topk: scan_common.h, shared with prune_finish.hip)
 
 // A second, dense segment of the same select launch (blockIdx.y == 1): the pruned search's
 // exact fresh-row tail, selected in the seed select's launch instead of a serial one of its own.

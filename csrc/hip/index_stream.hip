@@ -110,7 +110,12 @@ __device__ __forceinline__ float max16(const float (&v)[16]) {
 // workgroup PACK b + p does (xcd_remap applied to b): no barrier, no shared state, its own LDS
 // stage.  A group whose block lies past the n_lb = n_rblk * n_qblk blocks returns.
 // DEPTH_: sub-tiles in flight per wave (0: SGeo's).
-template <int FMT, int D, int ABL = 0, int PACK = 1, int DEPTH_ = 0>
+// NT_: the sub-tile fragments and block scales are loaded non-temporally (global_load ... nt).
+// Only for a form with NW == 1 (MX-fp4 at 384): there every sub-tile is read by exactly one wave,
+// once, so nothing is lost by not keeping it in L2 -- and the stream stops evicting what kernels
+// on other streams re-read from L2 (the encoder beside the scan).  Queries, centroids and
+// thresholds keep the default policy.
+template <int FMT, int D, int ABL = 0, int PACK = 1, int DEPTH_ = 0, bool NT_ = false>
 __global__ __launch_bounds__((64 * SGeo<FMT, D>::NW * PACK), 1) void scan_stream_kernel(
     const uint8_t* __restrict__ img, int n_valid, int rows_per_blk, const uint8_t* __restrict__ Q,
     const uint32_t* __restrict__ qsc, int NQ, int n_qblk, int n_lb, int xcd,
@@ -124,6 +129,7 @@ __global__ __launch_bounds__((64 * SGeo<FMT, D>::NW * PACK), 1) void scan_stream
   constexpr int NKS = S::NKS, NSC = S::NSC ? S::NSC : 1, REC = S::REC;
   constexpr int SETS = G::SETS, DEPTH = DEPTH_ ? DEPTH_ : G::DEPTH, STW = G::STW;
   static_assert(PACK >= 1 && G::NW * PACK <= 4, "one wave per SIMD");
+  static_assert(!NT_ || G::NW == 1, "non-temporal rows: a sub-tile must be read by one wave only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave_wg = threadIdx.x >> 6, h = lane >> 5;
   // (the thin form keeps its own plain expressions: the int8 scan is MFMA-bound and its
@@ -227,12 +233,18 @@ __global__ __launch_bounds__((64 * SGeo<FMT, D>::NW * PACK), 1) void scan_stream
     if constexpr (FMT == SF_I8) fts[d] = *reinterpret_cast<const float*>(r);
     const uint8_t* f = r + S::HDR + S::LB * lane;
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks)
-      fk[d][ks] = *reinterpret_cast<const i32x4s*>(f + 64 * S::LB * ks);
+    for (int ks = 0; ks < NKS; ++ks) {
+      const i32x4s* fp = reinterpret_cast<const i32x4s*>(f + 64 * S::LB * ks);
+      if constexpr (NT_) fk[d][ks] = __builtin_nontemporal_load(fp);
+      else fk[d][ks] = *fp;
+    }
     if constexpr (FMT != SF_I8) {
 #pragma unroll
-      for (int j = 0; j < NSC; ++j)
-        fsc[d][j] = *reinterpret_cast<const uint32_t*>(r + S::FRAG + 256 * j + 4 * lane);
+      for (int j = 0; j < NSC; ++j) {
+        const uint32_t* sp = reinterpret_cast<const uint32_t*>(r + S::FRAG + 256 * j + 4 * lane);
+        if constexpr (NT_) fsc[d][j] = __builtin_nontemporal_load(sp);
+        else fsc[d][j] = *sp;
+      }
     }
   };
 
@@ -829,8 +841,8 @@ struct CentArgs {   // the MX-fp4 centroid test's inputs (all nullptr: off)
 };
 
 // WIDE: the CU-granular form (PACK = 4 / NW thin workgroups per workgroup; a 4-wave thin form is
-// its own CU-granular form); DEPTH_: sub-tiles in flight (0: SGeo's)
-template <int F, int D, int ABL = 0, bool WIDE = false, int DEPTH_ = 0>
+// its own CU-granular form); DEPTH_: sub-tiles in flight (0: SGeo's); NT_: non-temporal row loads
+template <int F, int D, int ABL = 0, bool WIDE = false, int DEPTH_ = 0, bool NT_ = false>
 static int launch_stream(const void* img, int n_valid, int rows_per_blk, int n_rblk, const void* Q,
                          const void* qsc, int NQ, const float* thr, float* cand_s, int* cand_i,
                          int* cand_n, int cap, int xcd, hipStream_t st, const int* skip,
@@ -839,8 +851,8 @@ static int launch_stream(const void* img, int n_valid, int rows_per_blk, int n_r
   constexpr int PACK = WIDE ? 4 / G::NW : 1;
   const int n_qblk = (NQ + G::QPB - 1) / G::QPB, n_lb = n_rblk * n_qblk;
   constexpr int lds = G::STAGE * G::NW * PACK;
-  if (lds > 64 * 1024) set_max_lds<scan_stream_kernel<F, D, ABL, PACK, DEPTH_>>(lds);
-  hipLaunchKernelGGL((scan_stream_kernel<F, D, ABL, PACK, DEPTH_>), dim3((n_lb + PACK - 1) / PACK),
+  if (lds > 64 * 1024) set_max_lds<scan_stream_kernel<F, D, ABL, PACK, DEPTH_, NT_>>(lds);
+  hipLaunchKernelGGL((scan_stream_kernel<F, D, ABL, PACK, DEPTH_, NT_>), dim3((n_lb + PACK - 1) / PACK),
                      dim3(64 * G::NW * PACK), lds, st, (const uint8_t*)img, n_valid, rows_per_blk,
                      (const uint8_t*)Q, (const uint32_t*)qsc, NQ, n_qblk, n_lb, xcd, thr, cand_s,
                      cand_i, cand_n, cap, skip, gate, gate_want, runs, (const uint8_t*)ca.c4,
@@ -855,20 +867,25 @@ static int launch_stream(const void* img, int n_valid, int rows_per_blk, int n_r
 // workspace); gate != nullptr: the launch runs only if *gate == gate_want; runs (optional) is
 // incremented once by a launch that ran.  wide: the CU-granular form (scan_stream_kernel PACK:
 // ceil(n_rblk n_qblk / PACK) workgroups, each a whole CU) instead of the thin one.  depth: sub-tiles
-// in flight per wave, 0 = the form's default; 4 and 5 exist for MX-fp4 at dim 384.
+// in flight per wave, 0 = the form's default; 4 and 5 exist for MX-fp4 at dim 384.  nt: the
+// non-temporal row stream (scan_stream_kernel NT_), which exists for MX-fp4 at dim 384 at the
+// default depth only -- the one form whose sub-tiles are each read by a single wave.
 int symb_index_scan_stream(const void* img, int n_valid, int alloc_rows, int rows_per_blk,
                            int n_rblk, const void* Q, const void* qsc, int NQ, const float* thr,
                            float* cand_s, int* cand_i, int* cand_n, int cap, int xcd,
                            hipStream_t st, const int* skip, int dim, int form, const int* gate,
                            int gate_want, int zero_cnt, int* runs, const void* cent4,
                            const void* centqs, const float* centR, const float* bounds4, int wide,
-                           int depth) {
+                           int depth, int nt) {
   if (NQ <= 0) return 0;
-  if (wide < 0 || wide > 1) return -1;
+  if (wide < 0 || wide > 1 || nt < 0 || nt > 1) return -1;
+  static_assert(SGeo<SF_MX4, 384>::NW == 1, "the non-temporal form reads each sub-tile once");
+  if (nt && !(form == 1 && dim == 384)) return -1;
   if (depth == SGeo<SF_MX4, 384>::DEPTH && form == 1 && dim == 384) depth = 0;
   if (depth != 0 && !(form == 1 && dim == 384 && (depth == 4 || depth == 5))) return -1;
   // (the ablations exist in the thin form at the default depth)
-  if ((depth != 0 || wide) && g_stream_abl != 0) return -1;
+  if ((depth != 0 || wide || nt) && g_stream_abl != 0) return -1;
+  if (nt && depth != 0) return -1;
   if (cent4 != nullptr && (form != 1 || centqs == nullptr || centR == nullptr || bounds4 == nullptr))
     return -1;
   const CentArgs ca{cent4, centqs, centR, bounds4};
@@ -889,6 +906,13 @@ int symb_index_scan_stream(const void* img, int n_valid, int alloc_rows, int row
   (g_stream_abl == 1   ? L(F, D_, 1, false, 0)    \
    : g_stream_abl == 2 ? L(F, D_, 2, false, 0)    \
                        : LW(F, D_, 0))
+  if (nt)
+    return wide ? (launch_stream<SF_MX4, 384, 0, true, 0, true>(
+                      img, n_valid, rows_per_blk, n_rblk, Q, qsc, NQ, thr, cand_s, cand_i, cand_n,
+                      cap, xcd, st, skip, gate, gate_want, runs, ca))
+                : (launch_stream<SF_MX4, 384, 0, false, 0, true>(
+                      img, n_valid, rows_per_blk, n_rblk, Q, qsc, NQ, thr, cand_s, cand_i, cand_n,
+                      cap, xcd, st, skip, gate, gate_want, runs, ca));
   if (depth == 4) return wide ? L(SF_MX4, 384, 0, true, 4) : L(SF_MX4, 384, 0, false, 4);
   if (depth == 5) return wide ? L(SF_MX4, 384, 0, true, 5) : L(SF_MX4, 384, 0, false, 5);
   if (dim == 384) return form ? LD(SF_MX4, 384) : LD(SF_I8, 384);
