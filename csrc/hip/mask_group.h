@@ -1,5 +1,5 @@
-// The per-query mask words of the grouped masked scans (bf16: index_filter_group.hip; fp8:
-// index_filter_group_fp8.hip): mask8 is uint64 [n_words][MASK_GROUPS], 64 bytes per 64-row tile,
+// The per-query mask words of the masked scans' GROUPED forms (bf16: filter_scan.h; fp8:
+// fp8_filter_scan.h, fp8_emit.h): mask8 is uint64 [n_words][MASK_GROUPS], 64 bytes per 64-row tile,
 // slot g = the mask word of group g.  The eight words of a tile are wave-uniform and come by one
 // hand-issued scalar load (as sload_u64, scan_common.h); a lane then picks its group's word.
 #pragma once

@@ -1,4 +1,4 @@
-"""The masked e4m3 list scan (csrc/hip/index_filter_fp8.hip) and the filtered search of a GPU fp8
+"""The masked e4m3 list scan (csrc/hip/fp8_filter_scan.h) and the filtered search of a GPU fp8
 shard built on it, against ops/reference.filtered_topk_ref over the DECODED rows and queries (the
 MFMA sums exact e4m3 products in fp32), against the unfiltered fp8 search, and against the fp8
 list scan over the gathered rows.

@@ -1,4 +1,4 @@
-"""The masked list scan (csrc/hip/index_filter.hip) and the filtered search built on it, against
+"""The masked list scan (csrc/hip/filter_scan.h) and the filtered search built on it, against
 ops/reference.filtered_topk_ref and against the unfiltered list scan over the gathered rows.
 
 Shapes are the smallest at which the kernel can go wrong: 64 * 37 + 19 rows (a partial last tile,

@@ -1,7 +1,7 @@
-"""The grouped masked e4m3 list scan (csrc/hip/index_filter_group_fp8.hip) and the search of a GPU
+"""The grouped masked e4m3 list scan (csrc/hip/fp8_filter_scan.h, GROUPED) and the search of a GPU
 fp8 shard under a mask per query built on it: against ops/reference.grouped_filtered_topk_ref over
 the DECODED rows and queries (the MFMA sums exact e4m3 products in fp32), and -- bit for bit in
-scores -- against the single-mask fp8 search (index_filter_fp8.hip) of each group's queries under
+scores -- against the single-mask fp8 search (the same kernel) of each group's queries under
 that group's mask, which the existing tests pin to the oracle.
 
 Shapes are test_filter_fp8_gpu.py's and test_filter_group_gpu.py's: 64 * 37 + 19 rows (a partial

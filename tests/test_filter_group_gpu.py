@@ -1,6 +1,6 @@
-"""The grouped masked list scan (csrc/hip/index_filter_group.hip) and the search under a mask per
+"""The grouped masked list scan (csrc/hip/filter_scan.h, GROUPED) and the search under a mask per
 query built on it: against ops/reference.grouped_filtered_topk_ref, and -- bit for bit in scores --
-against the single-mask scan (index_filter.hip) of each group's queries under that group's mask.
+against the single-mask scan (the same kernel) of each group's queries under that group's mask.
 
 Shapes are test_filter_gpu.py's, the smallest at which the kernel can go wrong: 64 * 37 + 19 rows
 (a partial last tile, few workgroups) and 20 011 rows (several workgroups, slices longer than the

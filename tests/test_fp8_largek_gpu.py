@@ -1,4 +1,4 @@
-"""The emitting e4m3 scan (csrc/hip/index_emit_fp8.hip) and the searches built on it: top-k for
+"""The emitting e4m3 scan (csrc/hip/fp8_emit.h) and the searches built on it: top-k for
 32 < k <= 128 on a GPU fp8 shard, unmasked, under a row mask or over tombstones, with no chunked
 matmul from FP8_LARGE_K_MIN_ROWS visible rows on.
 
@@ -12,7 +12,7 @@ Kernel-level tests fix the set the kernel must emit from the fp32 reference alon
 of a query is the midpoint of the largest gap between consecutive sorted reference scores among
 ranks [64, 192), asserted to be at least GAP_MIN first.  GAP_MIN = max(1e-4, 4 * LIST_SCAN_ERR),
 where LIST_SCAN_ERR is the largest |raw / S^2 - fp32 reference| of the masked e4m3 LIST scan
-(index_filter_fp8.hip, which this change does not touch; kmax 32, every candidate slot of 300
+(fp8_filter_scan.h, which this change does not touch; kmax 32, every candidate slot of 300
 queries, an all-ones and a uniform 50 % mask) measured on an MI355X over these very shards, all
 five widths, both sizes: 8.70e-6 at D = 256, falling with the width to 2.7e-6 at 1024
 (LIST_SCAN_ERR below rounds the largest up).  4 x 8.8e-6 = 3.5e-5 is below 1e-4, so GAP_MIN stays

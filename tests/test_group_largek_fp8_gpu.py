@@ -1,4 +1,4 @@
-"""The grouped emitting e4m3 scan (csrc/hip/index_emit_group_fp8.hip) and the search built on it:
+"""The grouped emitting e4m3 scan (csrc/hip/fp8_emit.h, GROUPED) and the search built on it:
 top-k for 32 < k <= 128 on a GPU fp8 shard under a mask PER QUERY, one scan per chunk of up to
 eight masks instead of one masked emitting search per mask.
 
@@ -16,7 +16,7 @@ sets fixed from the fp32 reference (decoded rows, decoded e4m3 queries) use the 
 the constants of test_fp8_largek_gpu.py: a query's threshold is the midpoint of the largest gap
 between consecutive sorted reference scores, under its OWN mask, among ranks [64, 192), asserted
 to be at least GAP_MIN = max(1e-4, 4 * LIST_SCAN_ERR) first.  LIST_SCAN_ERR = 8.8e-6 is the
-largest |raw / S^2 - fp32 reference| of the masked e4m3 list scan (index_filter_fp8.hip, which
+largest |raw / S^2 - fp32 reference| of the masked e4m3 list scan (fp8_filter_scan.h, which
 this change does not touch) measured there over these very shards; test 1 below (same row, same
 score as index_scan_emit_fp8, which that module pins to the list scan) is what lets it carry
 over.  Membership carries no tolerance.  Search-level tolerances are that module's _check_out
