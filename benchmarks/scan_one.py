@@ -38,10 +38,12 @@ def main() -> None:
                          "centroid test off), e.g. 0:1,0:0")
     ap.add_argument("--reserve-sweep", default="",
                     help="--tier mx4 on the stream image: time the scan's forms in one process, "
-                         "interleaved: comma list of wide:R:depth[:nt] (wide 0 = the thin form, 1 "
-                         "= the CU-granular one; R = CUs left free, which sizes the block grid; "
-                         "depth 0 = the kernel's default; nt 1 = the non-temporal row stream, "
-                         "default 0), e.g. 0:0:0,1:0:0,1:64:0,1:64:4,1:96:0:1")
+                         "interleaved: comma list of wide:R:depth[:nt[:prefix]] (wide 0 = the thin "
+                         "form, 1 = the CU-granular one; R = CUs left free, which sizes the block "
+                         "grid; depth 0 = the kernel's default; nt 1 = the non-temporal row "
+                         "stream, default 0; prefix 2 / 3 = the prefix form reading that many "
+                         "k-steps per record, at the headline's prefix threshold, default 0), "
+                         "e.g. 0:0:0,1:0:0,1:64:0,1:64:4,1:96:0:1,1:96:6:1:3")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--thr-add", type=float, default=0.0,
                     help="added to the scan's thresholds (e.g. 10: no row emits -- kernel-only timing)")
@@ -128,19 +130,32 @@ def main() -> None:
         if a.tier != "mx4" or shard.img_mx4 is None:
             raise SystemExit("--reserve-sweep times the MX-fp4 stream scan (--tier mx4)")
         sweep = [tuple(int(x) for x in f.split(":")) for f in a.reserve_sweep.split(",")]
-        sweep = [f + (0,) * (4 - len(f)) for f in sweep]   # (nt defaults to 0)
+        sweep = [f + (0,) * (5 - len(f)) for f in sweep]   # (nt and prefix default to 0)
         from codename_symbiont_amd.ops import kernels as K
         n_cus = shard._n_cus()
         kw = shard._cent_args(m4)
 
-        def scan_form(wide, R, depth, nt):
+        # the headline's prefix thresholds T - mP - qR XR (profiles/prefix_tier/README.md), as
+        # thr4 above is the headline's T - margin4
+        thr_p = {k: torch.full_like(m4["thr4"], v + a.thr_add) for k, v in ((3, 0.276), (2, 0.160))}
+
+        def rec_bytes(prefix):
+            """bytes the scan reads per 32-row record: every k-step and scale dword, or the
+            prefix form's k-steps and the scale dwords that hold their scales"""
+            nks = prefix or a.dim // 64
+            return nks * 1024 + (nks + 3) // 4 * 256
+
+        def scan_form(wide, R, depth, nt, prefix):
             _, rpb, nrb = shard._i8_geometry(n, a.nq, n_cus, R)
             P["cnt"].zero_()
+            pk = dict(prefix=prefix, pbounds=shard.mx4_pbounds) if prefix else {}
             K.index_scan_stream(shard.img_mx4.data_ptr(), n, shard.img_mx4.shape[0] * STREAM_SUB,
                                 rpb, nrb, m4["q4"].data_ptr(), m4["qs4"].data_ptr(), a.nq,
-                                m4["thr4"].data_ptr(), P["cs"].data_ptr(), P["ci"].data_ptr(),
+                                (thr_p[prefix] if prefix else m4["thr4"]).data_ptr(),
+                                P["cs"].data_ptr(), P["ci"].data_ptr(),
                                 P["cnt"].data_ptr(), P["cap"], 1, st, dim=a.dim, form=1,
-                                wide=wide, depth=depth, nt=nt, **kw)
+                                wide=wide, depth=depth, nt=nt, **pk,
+                                **(shard._cent_args(m4, prefix=True) if prefix else kw))
             return rpb, nrb
 
         times = {f: [] for f in sweep}
@@ -157,10 +172,13 @@ def main() -> None:
         for f, ts in times.items():
             ms = sorted(ts)[len(ts) // 2]
             print(json.dumps({"bench": "scan_one", "kernel": "stream-mx4", "wide": f[0],
-                              "reserve": f[1], "depth": f[2], "nt": f[3], "rows": n, "nq": a.nq, "dim": a.dim,
+                              "reserve": f[1], "depth": f[2], "nt": f[3], "prefix": f[4],
+                              "rows": n, "nq": a.nq, "dim": a.dim,
                               "queries": a.queries, "ms": round(ms, 3),
                               "ms_all": [round(t, 3) for t in ts],
-                              "TBps": round(n * nbytes / ms / 1e9, 2), "n_rblk": geo[f][1],
+                              "GB": round(n / STREAM_SUB * rec_bytes(f[4]) / 1e9, 2),
+                              "TBps": round(n / STREAM_SUB * rec_bytes(f[4]) / ms / 1e9, 2),
+                              "prefix_runs": shard.prefix_runs, "n_rblk": geo[f][1],
                               "rows_per_blk": geo[f][0],
                               "cand_mean": round(float(P["cnt"].float().mean()), 1)}), flush=True)
         return

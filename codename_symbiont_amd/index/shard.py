@@ -547,6 +547,20 @@ class HbmIndexShard:
                 self.rows_mx4 = torch.zeros(n_alloc, dim // 2, dtype=torch.uint8, device=self.device)
                 self.sc_mx4 = torch.zeros(n_alloc, 16, dtype=torch.uint8, device=self.device)
             self.mx4_bounds = torch.zeros(2, dtype=torch.float32, device=self.device)
+        # the prefix tier (_pruned_begin): the fp4 stream scan over the first prefix_ksteps
+        # k-steps (64 dims each) of every record.  mx4_pbounds = (E_P, X_P, XR), the maxima over
+        # every row written of |x_P - x~_P|, |x~_P| and |x_R|, tracked beside mx4_bounds for this
+        # one prefix length (SYMB_PREFIX_KSTEPS for A/B runs); None: not tracked, the tier is off
+        self.prefix_ksteps = int(os.environ.get("SYMB_PREFIX_KSTEPS", "") or self.PREFIX_KSTEPS)
+        self.mx4_pbounds = None
+        if self.img_mx4 is not None and dim == 384 and self.prefix_ksteps in (2, 3):
+            self.mx4_pbounds = torch.zeros(3, dtype=torch.float32, device=self.device)
+        self.prefix_tier = int(os.environ.get("SYMB_PREFIX_TIER", "") or self.PREFIX_TIER)
+        # the share of mP the tier's choice allows between a row's prefix estimate and its exact
+        # partial score (PREFIX_BAND; SYMB_PREFIX_BAND for A/B runs, 1 = the worst case)
+        self.prefix_band = float(os.environ.get("SYMB_PREFIX_BAND", "") or self.PREFIX_BAND)
+        self._pfx_tot = None     # searches whose first tier was the prefix scan (device int32 [1])
+        self._pfx_last = None
         self.count = 0      # rows reserved (payload slots exist)
         # rows searches may read: published only after their writes are ENQUEUED on the stream
         # the scans share, so a search racing an upsert in another thread never scans a reserved
@@ -705,6 +719,10 @@ class HbmIndexShard:
             rec, nr = R.stream_mx4_ref(src)
             w = nr[r0 - g0 * STREAM_SUB:r1 - g0 * STREAM_SUB]
             torch.maximum(self.mx4_bounds, w[:, :2].amax(0), out=self.mx4_bounds)
+            if self.mx4_pbounds is not None:
+                pn = R.mx4_prefix_norms_ref(src[r0 - g0 * STREAM_SUB:r1 - g0 * STREAM_SUB],
+                                            self.prefix_ksteps)
+                torch.maximum(self.mx4_pbounds, pn[:, [0, 1, 3]].amax(0), out=self.mx4_pbounds)
         else:
             rec, err, xtn = R.stream_i8_ref(src)
             # (every row of the re-imaged sub-tiles: their shared scale may have changed)
@@ -749,9 +767,11 @@ class HbmIndexShard:
         if self.mx4_on:
             if self.img_mx4 is not None:
                 if gpu:
+                    pb = self.mx4_pbounds
                     h.quant_stream_mx4(self.rows.data_ptr(), r0, rp, n, self.dim,
                                        self.img_mx4.data_ptr(), 0, 0, self.mx4_bounds.data_ptr(),
-                                       0, st)
+                                       0, st, pbounds=0 if pb is None else pb.data_ptr(),
+                                       nkp=0 if pb is None else self.prefix_ksteps)
                 elif rows is None:
                     self._stream_subtiles_cpu(self.img_mx4, 1, r0, r0 + n)
                 else:
@@ -768,13 +788,29 @@ class HbmIndexShard:
                 self.rows_mx4.index_copy_(0, ri, img4)
                 self.sc_mx4.index_copy_(0, ri, sc4)
 
-    def mx4_query_image(self, q_unit: torch.Tensor):
+    @property
+    def prefix_on(self) -> bool:
+        """The shard tracks the prefix tier's bounds (mx4_pbounds)."""
+        return self.mx4_pbounds is not None
+
+    @property
+    def prefix_runs(self) -> int:
+        """Searches whose first tier was the prefix scan (a device counter; this reads it back)."""
+        return 0 if self._pfx_tot is None else int(self._pfx_tot.item())
+
+    def mx4_query_image(self, q_unit: torch.Tensor, prefix: bool = False):
         """(nibbles, scale record, margin) of unit queries for the MX-fp4 tier: the stream form
         (quant_stream_mx4: [NQ][D / 2], [NQ][2 NSC] dwords) or the LDS-ring form (quant_rows_mx4:
-        [NQ][192], [NQ][16] bytes); margin = |q| E4 + |q - q~| X4 + 1e-5."""
+        [NQ][192], [NQ][16] bytes); margin = |q| E4 + |q - q~| X4 + 1e-5.
+        ``prefix`` (a shard with prefix bounds): also (mP, qR), the prefix tier's margin
+        |q_P| E_P + |q_P - q~_P| X_P + 1e-5 and |q_R|."""
         NQ, dev = q_unit.shape[0], self.device
+        if prefix and (self.mx4_pbounds is None or self.img_mx4 is None):
+            raise ValueError("mx4_query_image: the shard tracks no prefix bounds")
         q4 = torch.empty(NQ, self.dim // 2, dtype=torch.uint8, device=dev)
         m4 = torch.empty(NQ, dtype=torch.float32, device=dev)
+        mP = torch.empty(NQ, dtype=torch.float32, device=dev) if prefix else None
+        qR = torch.empty(NQ, dtype=torch.float32, device=dev) if prefix else None
         if self.img_mx4 is None:
             qs4 = torch.empty(NQ, 16, dtype=torch.uint8, device=dev)
             self._mx4_image(q_unit, q4, qs4, self.mx4_bounds, margin=m4)
@@ -784,16 +820,23 @@ class HbmIndexShard:
         if dev.type == "cuda":
             from ..ops._ext import hip, stream_handle
 
+            pk = dict(pbounds=self.mx4_pbounds.data_ptr(), nkp=self.prefix_ksteps,
+                      mP=mP.data_ptr(), qR=qR.data_ptr()) if prefix else {}
             hip().quant_stream_mx4(q_unit.data_ptr(), 0, 0, NQ, self.dim, 0, q4.data_ptr(),
                                    qs4.data_ptr(), self.mx4_bounds.data_ptr(), m4.data_ptr(),
-                                   stream_handle(dev))
-            return q4, qs4, m4
-        from ..ops.reference import stream_mx4_query_ref
+                                   stream_handle(dev), **pk)
+            return (q4, qs4, m4, mP, qR) if prefix else (q4, qs4, m4)
+        from ..ops.reference import mx4_prefix_norms_ref, stream_mx4_query_ref
 
         img, qs, _, nr = stream_mx4_query_ref(q_unit)
         q4.copy_(img)
         qs4.copy_(qs)
         m4.copy_(nr[:, 2] * self.mx4_bounds[0] + nr[:, 0] * self.mx4_bounds[1] + 1e-5)
+        if prefix:
+            pn = mx4_prefix_norms_ref(q_unit, self.prefix_ksteps)
+            mP.copy_(pn[:, 2] * self.mx4_pbounds[0] + pn[:, 0] * self.mx4_pbounds[1] + 1e-5)
+            qR.copy_(pn[:, 3])
+            return q4, qs4, m4, mP, qR
         return q4, qs4, m4
 
     # ------------------------------------------------------------------ inserts
@@ -865,10 +908,13 @@ class HbmIndexShard:
         from ..ops._ext import hip, stream_handle
 
         m4 = self.img_mx4 is not None
+        pb = self.mx4_pbounds if m4 else None
         hip().append_rows(src.data_ptr(), n, self.dim, self.rows.data_ptr(), r0,
                           self.img_i8.data_ptr(), self.i8_bounds.data_ptr(),
                           self.img_mx4.data_ptr() if m4 else 0,
-                          self.mx4_bounds.data_ptr() if m4 else 0, stream_handle(self.device))
+                          self.mx4_bounds.data_ptr() if m4 else 0, stream_handle(self.device),
+                          pb4=0 if pb is None else pb.data_ptr(),
+                          nkp=0 if pb is None else self.prefix_ksteps)
         return True
 
     def _split_at_write(self) -> bool:
@@ -2409,8 +2455,13 @@ class HbmIndexShard:
         m_seed = -(-nv // self.SEED_DIV) * TILE_ROWS
         ld = _round_up(m_seed + (tcap if dense_tail else 0), 4)
         S = torch.empty(NQ, ld, device=dev)
+        # the prefix tier is enqueued too (step 3): the same launch keeps each score's partial sum
+        # over the prefix dims for its choice
+        pfx = self._prefix_enqueued(dense_tail)
+        SP = torch.empty(NQ, ld, device=dev) if pfx else None
+        pk = dict(outp=SP.data_ptr(), prefix_dims=64 * self.prefix_ksteps) if pfx else {}
         h.dense_scores(self.rows.data_ptr(), self.dim, 0, m_seed, t0, tcap if dense_tail else 0,
-                       q_unit.data_ptr(), NQ, S.data_ptr(), ld, st, ts=ts, div=self.SEED_DIV)
+                       q_unit.data_ptr(), NQ, S.data_ptr(), ld, st, ts=ts, div=self.SEED_DIV, **pk)
         thr0 = torch.empty(NQ, dtype=torch.float32, device=dev)
         seed_s = torch.empty(NQ, k, device=dev)
         seed_i = torch.empty(NQ, k, dtype=torch.int32, device=dev)
@@ -2484,13 +2535,31 @@ class HbmIndexShard:
         nvf = flags[self.WS_NV:self.WS_NV + 1]
         n_probe = TILE_ROWS * -(-(m_seed // TILE_ROWS) // 4)
         if self.mx4_on and self.prune_route and dense_tail:
-            q4, qs4, m4 = self.mx4_query_image(q_unit)
+            q4, qs4, m4, *pq = self.mx4_query_image(q_unit, prefix=pfx)
             thr4 = torch.empty(NQ, dtype=torch.float32, device=dev)
             h.mx4_select(NQ, T.data_ptr(), m4.data_ptr(), margin.data_ptr(), S.data_ptr(), m_seed,
                          float(t0) / n_probe, tcs_p, tcap, self.MX4_LIMIT_FRAC * cap,
                          thr4.data_ptr(), nvf.data_ptr(), st, ld=ld, tile_stride=4, tail_ld=ld,
                          nv_zeroed=True)
             ctx["mx4"] = dict(q4=q4, qs4=qs4, thr4=thr4, nv=nvf)
+            if pfx:
+                # 3'. the prefix tier (mx4_prefix_select): where T stands so high that even with
+                #     the remainder dims bounded by |q_R| XR the prefix estimate separates the
+                #     rows that can matter -- the same self / near-duplicate regime -- the fp4 scan
+                #     reads only the first prefix_ksteps k-steps of every record, half the bytes
+                #     at 3.  A second flag word says which fp4 form runs (0: prefix, 1: whole
+                #     rows); the fp4 tier's one launch reads it and runs that form.
+                mP, qR = pq
+                thrP = torch.empty(NQ, dtype=torch.float32, device=dev)
+                nvp = flags[self.WS_PFX:self.WS_PFX + 1]
+                h.mx4_prefix_select(NQ, T.data_ptr(), mP.data_ptr(), qR.data_ptr(),
+                                    self.mx4_pbounds.data_ptr(), margin.data_ptr(), S.data_ptr(),
+                                    SP.data_ptr(), m_seed, float(t0) / n_probe, tcs_p,
+                                    SP.data_ptr() + 4 * m_seed, tcap,
+                                    inf if self.prefix_tier == 2 else self.MX4_LIMIT_FRAC * cap,
+                                    thrP.data_ptr(), nvp.data_ptr(), st, ld=ld, tile_stride=4,
+                                    tail_ld=ld, nvp_zeroed=True, band=self.prefix_band)
+                ctx["mx4"].update(thrP=thrP, nvp=nvp)
             if self.img_mx4 is not None and self.mx4_centroid:
                 # the query-side bound (index_stream.hip mx4_centroids_kernel): per 32-query set
                 # the centroid image and radius R, so the scan skips a set's MFMAs on sub-tiles
@@ -2569,17 +2638,48 @@ class HbmIndexShard:
     # tier's "not viable" flag, the sample's and the final select's overflow flags, and a slot
     # the dense selects may write (they never overflow)
     WS_DENSE, WS_NV, WS_SAMPLE_OVF, WS_OVF, WS_SCRATCH, WS_FLAGS = 0, 1, 2, 3, 4, 8
+    WS_PFX = 5   # the fp4 tier's form: 0 the prefix scan, 1 the whole-row scan (mx4_prefix_select)
+
+    # the prefix tier's defaults: k-steps read per record, on / off (the prefix form runs at its
+    # deep depth, ops/kernels.py SCAN_PREFIX_DEEP; profiles/prefix_tier/README.md has the
+    # measurements)
+    PREFIX_KSTEPS = 3
+    PREFIX_TIER = 1   # (2: the candidate estimate is skipped, the tier runs whenever thrP > 0; A/B)
+    # The tier's choice counts probe rows whose exact partial score reaches thrP - PREFIX_BAND mP.
+    # mP bounds |q~_P . x~_P - q_P . x_P| by Cauchy-Schwarz with the maxima over every row: the
+    # worst case (band 1) needs each row's quantisation error to point along the query.  Errors
+    # of unrelated direction reach mP / sqrt(64 PREFIX_KSTEPS) at one standard deviation (0.07 mP
+    # at 192 dims), so a quarter of mP is about 3.5 of them.  At band 1 the headline's thrP - mP
+    # is 0.08, 2.2 standard deviations of the bulk's partial scores: the estimate is 1.4M
+    # candidates per query where the scan emits none beyond the whole-row scan's, and the tier
+    # never ran (0 of 100 batches).  The choice is an estimate either way: a batch that emits
+    # more than foreseen overflows PRUNE_CAP and takes the exact fall-back.
+    PREFIX_BAND = 0.25
+
+    def _prefix_enqueued(self, dense_tail: bool) -> bool:
+        """Does this search enqueue the prefix scan beside the whole-row fp4 scan?  Only on a
+        shard that tracked the prefix bounds over every row it wrote, and where both forms exist
+        behind the second gate: the non-temporal stream scans at the default depth."""
+        from ..ops import kernels as K
+
+        return bool(self.prefix_tier and self.mx4_pbounds is not None and self.mx4_on
+                    and self.img_mx4 is not None and self.prune_route and dense_tail
+                    and self.scan_nt and K.scan_stream_nt_ok(self.dim, 1, self.scan_depth)
+                    and K.scan_stream_prefix_ok(self.dim, 1, 0, self.prefix_ksteps))
 
     # the MX-fp4 tier's query-side centroid test (SYMB_MX4_CENTROID=0: off, A/B)
     mx4_centroid = os.environ.get("SYMB_MX4_CENTROID", "1") not in ("", "0")
 
-    def _cent_args(self, m4) -> dict:
+    def _cent_args(self, m4, prefix: bool = False) -> dict:
         """index_scan_stream's centroid-test arguments for an MX-fp4 query context (none when the
-        context has no centroids)."""
+        context has no centroids).  ``prefix``: for the prefix scan, whose rows' norm bound is
+        X_P = mx4_pbounds[1] (the kernel reads element 1 of ``bounds4``): |x~_P| <= X_P <= X4, so
+        the test c~_P . x~_P + R_s X_P skips more than with X4."""
         if m4 is None or "c4" not in m4:
             return {}
+        b = self.mx4_pbounds if prefix else self.mx4_bounds
         return dict(cent4=m4["c4"].data_ptr(), centqs=m4["cqs"].data_ptr(),
-                    centR=m4["cR"].data_ptr(), bounds4=self.mx4_bounds.data_ptr())
+                    centR=m4["cR"].data_ptr(), bounds4=b.data_ptr())
 
     # default of ``scan_reserve`` (profiles/r7_reserve/README.md has the sweep)
     SCAN_RESERVE = 96
@@ -2704,7 +2804,7 @@ class HbmIndexShard:
         # split tier): exactly one runs
         m4 = ctx.get("mx4")
         if m4 is not None:
-            for t in ("q4", "qs4", "thr4", "c4", "cqs", "cR"):
+            for t in ("q4", "qs4", "thr4", "c4", "cqs", "cR", "thrP"):
                 if t in m4:
                     m4[t].record_stream(cur)
         tier = None if m4 is None else m4["nv"]
@@ -2738,6 +2838,16 @@ class HbmIndexShard:
                         self._mx4_tot = torch.zeros(1, dtype=torch.int32, device=dev)
                     runs = self._mx4_tot.data_ptr()
                 depth = self.scan_depth if self.dim == 384 else 0
+                pk = {}
+                if "thrP" in m4:
+                    # one launch for the fp4 tier: the kernel reads the form word and runs the
+                    # prefix form (thrP, X_P in the centroid test) or the whole-row form (thr4)
+                    if self._pfx_tot is None:
+                        self._pfx_tot = torch.zeros(1, dtype=torch.int32, device=dev)
+                    depth = K.SCAN_PREFIX_DEEP[self.prefix_ksteps]
+                    pk = dict(prefix=self.prefix_ksteps, pbounds=self.mx4_pbounds,
+                              thr_prefix=m4["thrP"].data_ptr(), gate2=m4["nvp"].data_ptr(),
+                              runs2=self._pfx_tot.data_ptr())
                 K.index_scan_stream(self.img_mx4.data_ptr(), n_scan,
                                     self.img_mx4.shape[0] * STREAM_SUB, rows_per_blk, n_rblk,
                                     m4["q4"].data_ptr(), m4["qs4"].data_ptr(), NQ,
@@ -2746,8 +2856,8 @@ class HbmIndexShard:
                                     dim=self.dim, form=1, gate=m4["nv"].data_ptr(), gate_want=0,
                                     zero_cnt=0, runs=runs, wide=wide, depth=depth,
                                     nt=int(bool(self.scan_nt)
-                                           and K.scan_stream_nt_ok(self.dim, 1, depth)),
-                                    **self._cent_args(m4))
+                                           and (bool(pk) or K.scan_stream_nt_ok(self.dim, 1, depth))),
+                                    **pk, **self._cent_args(m4))
             else:
                 h.index_scan_i8(self.rows_mx4.data_ptr(), self.sc_mx4.data_ptr(), n_scan,
                                 self.rows_mx4.shape[0], rows_per_blk, n_rblk, m4["q4"].data_ptr(),
@@ -2794,6 +2904,8 @@ class HbmIndexShard:
         self._route_last = dense
         self._mx4_last = None if m4 is None else m4["nv"]   # 0: the MX-fp4 tier ran
         self._tier_last = tier   # 0 fp4, 1 int8 / split
+        # 0: the prefix form ran if an fp4 tier did (None: the prefix scan was not enqueued)
+        self._pfx_last = None if m4 is None else m4.get("nvp")
         if tier is not None and dev.type == "cuda":
             if flag is None:   # (no fused finish, or no device address for the pinned word)
                 flag = torch.empty(1, dtype=torch.int32, pin_memory=True)

@@ -643,19 +643,57 @@ def scan_stream_nt_ok(dim: int, form: int, depth: int = 0) -> bool:
     return int(form) == 1 and int(dim) == 384 and int(depth) in (0, 3)
 
 
-def index_scan_stream(*args, nt: int = 0, **kw) -> None:
-    """``_hip.index_scan_stream`` with the ``nt`` argument checked first: the non-temporal row
-    stream is refused, before the extension is touched, for every form that has none (the int8
-    image, widths 768 / 1024, depths 4 / 5 -- scan_stream_nt_ok).  Every other argument is passed
+# the prefix scan's depths (index_stream.hip symb_stream_prefix_depth): 3 (or 0, the default) and
+# the deep one that keeps the whole-row form's bytes in flight per wave
+SCAN_PREFIX_DEEP = {3: 6, 2: 8}
+
+
+def scan_stream_prefix_ok(dim: int, form: int, depth: int, prefix: int) -> bool:
+    """Does the stream scan have a prefix form (scan_stream_kernel NKP_) reading ``prefix``
+    k-steps?  Only MX-fp4 (form 1) at width 384, prefix 2 or 3, at depth 0 / 3 or the deep depth."""
+    return (int(form) == 1 and int(dim) == 384 and int(prefix) in SCAN_PREFIX_DEEP
+            and int(depth) in (0, 3, SCAN_PREFIX_DEEP[int(prefix)]))
+
+
+def index_scan_stream(*args, nt: int = 0, prefix: int = 0, pbounds=None, thr_prefix: int = 0,
+                      **kw) -> None:
+    """``_hip.index_scan_stream`` with the ``nt`` and ``prefix`` arguments checked first: the
+    non-temporal row stream is refused, before the extension is touched, for every form that has
+    none (the int8 image, widths 768 / 1024, depths 4 / 5 -- scan_stream_nt_ok), and so is the
+    prefix form (``prefix`` = 2 or 3 k-steps read per record; scan_stream_prefix_ok), which is
+    non-temporal always.  A prefix scan's thresholds are only meaningful with the prefix bounds
+    of the image it reads: ``pbounds`` (the shard's 3-float tensor) must be given with a nonzero
+    ``prefix``.  ``thr_prefix`` (a pointer to the prefix thresholds): the fp4 tier in one launch
+    that picks its form on the device from the word ``gate2`` (0: the prefix form at its deep
+    depth, else the whole-row form with ``thr``); ``pbounds`` then goes to the kernel as the
+    prefix form's row bound, otherwise it is not passed on.  Every other argument is passed
     through as the binding takes it (raw pointers, the stream handle)."""
-    nt = int(nt)
+    nt, prefix = int(nt), int(prefix)
     if nt not in (0, 1):
         raise ValueError(f"index_scan_stream: nt must be 0 or 1, got {nt}")
-    if nt:
-        dim, form, depth = kw.get("dim", 384), kw.get("form", 0), kw.get("depth", 0)
-        if not scan_stream_nt_ok(dim, form, depth):
-            raise ValueError(f"index_scan_stream: no non-temporal form for dim {dim}, form {form}, "
-                             f"depth {depth} (MX-fp4 at 384, default depth only)")
+    dim, form, depth = kw.get("dim", 384), kw.get("form", 0), kw.get("depth", 0)
+    if prefix:
+        if not scan_stream_prefix_ok(dim, form, depth, prefix):
+            raise ValueError(f"index_scan_stream: no prefix form for dim {dim}, form {form}, "
+                             f"depth {depth}, prefix {prefix} (MX-fp4 at 384, prefix 2 or 3, "
+                             f"depth 0 / 3 or {SCAN_PREFIX_DEEP})")
+        if pbounds is None:
+            raise ValueError("index_scan_stream: a prefix scan needs the image's prefix bounds")
+        if not nt:
+            raise ValueError("index_scan_stream: the prefix form is non-temporal (nt=1)")
+        if thr_prefix:
+            if int(depth) != SCAN_PREFIX_DEEP[prefix] or not kw.get("gate2"):
+                raise ValueError("index_scan_stream: the one-launch fp4 tier runs its prefix form "
+                                 f"at depth {SCAN_PREFIX_DEEP[prefix]} and needs the form word "
+                                 "(gate2)")
+            kw["thr_prefix"], kw["pbounds"] = int(thr_prefix), pbounds.data_ptr()
+    elif thr_prefix:
+        raise ValueError("index_scan_stream: thr_prefix without a prefix length")
+    elif nt and not scan_stream_nt_ok(dim, form, depth):
+        raise ValueError(f"index_scan_stream: no non-temporal form for dim {dim}, form {form}, "
+                         f"depth {depth} (MX-fp4 at 384, default depth only)")
+    if prefix:
+        kw["prefix"] = prefix
     hip().index_scan_stream(*args, nt=nt, **kw)
 
 

@@ -258,6 +258,46 @@ def mx4_codes_ref(x: torch.Tensor):
     return img, e, xt, norms
 
 
+def mx4_prefix_norms_ref(x: torch.Tensor, nkp: int) -> torch.Tensor:
+    """The prefix tier's norms of rows (or queries), split at dim 64 nkp (P = the first nkp
+    k-steps of the MX-fp4 scan, R = the rest): [n, 4] = (|x_P - x~_P|, |x~_P|, |x_P|, |x_R|), x~
+    the MX-fp4 image.  Rows raise the bounds (E_P, X_P, XR) to the maxima of columns 0, 1, 3;
+    a query's margin is mP = |q_P| E_P + |q_P - q~_P| X_P + 1e-5 and its qR column 3."""
+    p = 64 * int(nkp)
+    if not 0 < p <= x.shape[1]:
+        raise ValueError(f"mx4_prefix_norms_ref: nkp {nkp} for width {x.shape[1]}")
+    xf = x.float()
+    xt = mx4_codes_ref(x)[2]
+    return torch.stack([(xf[:, :p] - xt[:, :p]).norm(dim=1), xt[:, :p].norm(dim=1),
+                        xf[:, :p].norm(dim=1), xf[:, p:].norm(dim=1)], 1)
+
+
+def prefix_tier_choice_ref(T, m4, m8, mP, qR, XR, probe_s, probe_p, rate, tail_s, tail_p, limit,
+                           band=1.0):
+    """The first tier the pruned search takes (index_i8.hip mx4_select_kernel, then
+    mx4_prefix_select_kernel), as a torch composition: "prefix", "fp4" or "int8".
+    T / m4 / m8 / mP / qR: [NQ] (k-th score bound, fp4 margin, int8 margin, prefix margin, |q_R|);
+    probe_s / probe_p: [NQ, n] exact scores and exact partial scores (first dims) of the probe rows,
+    each standing for ``rate`` corpus rows; tail_s / tail_p: the same of the tail rows; limit: the
+    candidates per query a tier may add; band: the share of mP between a row's prefix estimate and
+    its exact partial score that the count allows (1 = the worst case).
+    Returns (name, thr4, thrP)."""
+    T, m4, m8 = T.float(), m4.float(), m8.float()
+    hi = (T - m8)[:, None]
+
+    def count(lo, ps, ts, pp=None, tp=None):
+        a = ((ps if pp is None else pp) >= lo[:, None]) & (ps < hi)
+        b = ((ts if tp is None else tp) >= lo[:, None]) & (ts < hi)
+        return a.sum(1).float() * float(rate) + b.sum(1).float()
+
+    thr4 = T - m4
+    fp4 = bool((count(T - 2.0 * m4, probe_s, tail_s) <= limit).all())
+    thrP = T - mP.float() - qR.float() * float(XR)
+    pfx = bool((torch.isfinite(thrP) & (thrP > 0)).all()) and bool(
+        (count(thrP - float(band) * mP.float(), probe_s, tail_s, probe_p, tail_p) <= limit).all())
+    return ("prefix" if fp4 and pfx else "fp4" if fp4 else "int8"), thr4, thrP
+
+
 # ---- the stream images (index_stream.hip): 32-row sub-tiles, fragment-major ----------------
 def _stream_frags(rowbytes: torch.Tensor) -> torch.Tensor:
     """Row-major image bytes [n, RB] (RB = 32 NKS) -> fragment-major [n_sub, NKS * 1024]: k-step

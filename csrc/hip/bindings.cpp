@@ -144,6 +144,12 @@ int symb_mx4_select(int NQ, const float* T, const float* margin4, const float* m
                     const float* probe_s, int n_cols, int ld, int tile_stride, float rate,
                     const float* tail_cs, int tail_cap, int tail_ld, float limit, float* thr4,
                     int* nv, hipStream_t st, int nv_zeroed);
+int symb_mx4_prefix_select(int NQ, const float* T, const float* mP, const float* qR,
+                           const float* pbounds, const float* margin8, const float* probe_s,
+                           const float* probe_p, int n_cols, int ld, int tile_stride, float rate,
+                           const float* tail_cs, const float* tail_cp, int tail_cap, int tail_ld,
+                           float limit, float* thrP, int* nvp, hipStream_t st, int nvp_zeroed,
+                           float band);
 int symb_i8_tile_rows_for(int dim, int heavy);
 // the streaming pruning scan (index_stream.hip)
 int symb_stream_rec_bytes(int dim, int form);
@@ -155,20 +161,23 @@ int symb_index_scan_stream(const void* img, int n_valid, int alloc_rows, int row
                            hipStream_t st, const int* skip, int dim, int form, const int* gate,
                            int gate_want, int zero_cnt, int* runs, const void* cent4,
                            const void* centqs, const float* centR, const float* bounds4, int wide,
-                           int depth, int nt);
+                           int depth, int nt, int prefix, const int* gate2, int gate2_want,
+                           int* runs2, const float* thr_prefix, const float* pbounds);
+int symb_stream_prefix_depth(int prefix);
 int symb_mx4_centroids(const void* Xq, const void* QS, int NQ, int dim, void* C4, void* CS,
                        float* R, hipStream_t st);
 int symb_append_rows(const void* src, int n, int dim, void* rows, int r0, void* img8, float* b8,
-                     void* img4, float* b4, hipStream_t st);
+                     void* img4, float* b4, hipStream_t st, float* pb4, int nkp);
 int symb_dense_scores(const void* X, int dim, const int* rows, int n_list, int ts, int div,
                       int r_lo, int n_range, const void* Q, int NQ, float* out, int ld,
-                      hipStream_t st);
+                      hipStream_t st, float* outp, int prefix_dims);
 int symb_quant_stream_i8(const void* X, int r0, const int* rows, int n, int dim, void* img,
                          float* bounds, hipStream_t st);
 int symb_prefill_candidates(int NQ, int r_lo, int n, int* cand_i, int* cand_n, int cap,
                             hipStream_t st);
 int symb_quant_stream_mx4(const void* X, int r0, const int* rows, int n, int dim, void* img,
-                          void* Xq, void* QS, float* bounds, float* margin, hipStream_t st);
+                          void* Xq, void* QS, float* bounds, float* margin, hipStream_t st,
+                          float* pbounds, int nkp, float* mP, float* qR);
 int symb_i8_split_queries_per_blk(int rsplit, int dim);
 int symb_mx4_config(int tile_rows);
 int symb_mx4_tile_rows();
@@ -687,13 +696,16 @@ PYBIND11_MODULE(_hip, m) {
                                 uptr cand_n, int cap, int xcd, uptr st, uptr skip, int dim,
                                 int form, uptr gate, int gate_want, int zero_cnt, uptr runs,
                                 uptr cent4, uptr centqs, uptr centR, uptr bounds4, int wide,
-                                int depth, int nt) {
+                                int depth, int nt, int prefix, uptr gate2, int gate2_want,
+                                uptr runs2, uptr thr_prefix, uptr pbounds) {
     check(symb_index_scan_stream(P<void>(img), n_valid, alloc_rows, rows_per_blk, n_rblk,
                                  P<void>(Q), P<void>(qsc), NQ, P<const float>(thr),
                                  P<float>(cand_s), P<int>(cand_i), P<int>(cand_n), cap, xcd, S(st),
                                  P<const int>(skip), dim, form, P<const int>(gate), gate_want,
                                  zero_cnt, P<int>(runs), P<void>(cent4), P<void>(centqs),
-                                 P<const float>(centR), P<const float>(bounds4), wide, depth, nt),
+                                 P<const float>(centR), P<const float>(bounds4), wide, depth, nt,
+                                 prefix, P<const int>(gate2), gate2_want, P<int>(runs2),
+                                 P<const float>(thr_prefix), P<const float>(pbounds)),
           "index_scan_stream");
   }, py::arg("img"), py::arg("n_valid"), py::arg("alloc_rows"), py::arg("rows_per_blk"),
      py::arg("n_rblk"), py::arg("Q"), py::arg("qsc"), py::arg("NQ"), py::arg("thr"),
@@ -701,7 +713,10 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("stream"), py::arg("skip") = 0, py::arg("dim") = 384, py::arg("form") = 0,
      py::arg("gate") = 0, py::arg("gate_want") = 0, py::arg("zero_cnt") = 1, py::arg("runs") = 0,
      py::arg("cent4") = 0, py::arg("centqs") = 0, py::arg("centR") = 0, py::arg("bounds4") = 0,
-     py::arg("wide") = 0, py::arg("depth") = 0, py::arg("nt") = 0);
+     py::arg("wide") = 0, py::arg("depth") = 0, py::arg("nt") = 0, py::arg("prefix") = 0,
+     py::arg("gate2") = 0, py::arg("gate2_want") = 0, py::arg("runs2") = 0,
+     py::arg("thr_prefix") = 0, py::arg("pbounds") = 0);
+  m.def("stream_prefix_depth", [](int prefix) { return symb_stream_prefix_depth(prefix); });
   m.def("mx4_centroids", [](uptr Xq, uptr QS, int NQ, int dim, uptr C4, uptr CS, uptr R, uptr st) {
     check(symb_mx4_centroids(P<void>(Xq), P<void>(QS), NQ, dim, P<void>(C4), P<void>(CS),
                              P<float>(R), S(st)),
@@ -709,20 +724,23 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("Xq"), py::arg("QS"), py::arg("NQ"), py::arg("dim"), py::arg("C4"), py::arg("CS"),
      py::arg("R"), py::arg("stream"));
   m.def("append_rows", [](uptr src, int n, int dim, uptr rows, int r0, uptr img8, uptr b8,
-                          uptr img4, uptr b4, uptr st) {
+                          uptr img4, uptr b4, uptr st, uptr pb4, int nkp) {
     check(symb_append_rows(P<void>(src), n, dim, P<void>(rows), r0, P<void>(img8), P<float>(b8),
-                           P<void>(img4), P<float>(b4), S(st)),
+                           P<void>(img4), P<float>(b4), S(st), P<float>(pb4), nkp),
           "append_rows");
   }, py::arg("src"), py::arg("n"), py::arg("dim"), py::arg("rows"), py::arg("r0"),
-     py::arg("img8"), py::arg("b8"), py::arg("img4"), py::arg("b4"), py::arg("stream"));
+     py::arg("img8"), py::arg("b8"), py::arg("img4"), py::arg("b4"), py::arg("stream"),
+     py::arg("pb4") = 0, py::arg("nkp") = 0);
   m.def("dense_scores", [](uptr X, int dim, uptr rows, int n_list, int r_lo, int n_range, uptr Q,
-                           int NQ, uptr out, int ld, uptr st, int ts, int div) {
+                           int NQ, uptr out, int ld, uptr st, int ts, int div, uptr outp,
+                           int prefix_dims) {
     check(symb_dense_scores(P<void>(X), dim, P<const int>(rows), n_list, ts, div, r_lo, n_range,
-                            P<void>(Q), NQ, P<float>(out), ld, S(st)),
+                            P<void>(Q), NQ, P<float>(out), ld, S(st), P<float>(outp), prefix_dims),
           "dense_scores");
   }, py::arg("X"), py::arg("dim"), py::arg("rows"), py::arg("n_list"), py::arg("r_lo"),
      py::arg("n_range"), py::arg("Q"), py::arg("NQ"), py::arg("out"), py::arg("ld"),
-     py::arg("stream"), py::arg("ts") = 0, py::arg("div") = 1);
+     py::arg("stream"), py::arg("ts") = 0, py::arg("div") = 1, py::arg("outp") = 0,
+     py::arg("prefix_dims") = 0);
   m.def("quant_stream_i8", [](uptr X, int r0, uptr rows, int n, int dim, uptr img, uptr bounds,
                               uptr st) {
     check(symb_quant_stream_i8(P<void>(X), r0, P<const int>(rows), n, dim, P<void>(img),
@@ -737,13 +755,33 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("NQ"), py::arg("r_lo"), py::arg("n"), py::arg("cand_i"), py::arg("cand_n"),
      py::arg("cap"), py::arg("stream"));
   m.def("quant_stream_mx4", [](uptr X, int r0, uptr rows, int n, int dim, uptr img, uptr Xq,
-                               uptr QS, uptr bounds, uptr margin, uptr st) {
+                               uptr QS, uptr bounds, uptr margin, uptr st, uptr pbounds, int nkp,
+                               uptr mP, uptr qR) {
     check(symb_quant_stream_mx4(P<void>(X), r0, P<const int>(rows), n, dim, P<void>(img),
                                 P<void>(Xq), P<void>(QS), P<float>(bounds), P<float>(margin),
-                                S(st)),
+                                S(st), P<float>(pbounds), nkp, P<float>(mP), P<float>(qR)),
           "quant_stream_mx4");
   }, py::arg("X"), py::arg("r0"), py::arg("rows"), py::arg("n"), py::arg("dim"), py::arg("img"),
-     py::arg("Xq"), py::arg("QS"), py::arg("bounds"), py::arg("margin"), py::arg("stream"));
+     py::arg("Xq"), py::arg("QS"), py::arg("bounds"), py::arg("margin"), py::arg("stream"),
+     py::arg("pbounds") = 0, py::arg("nkp") = 0, py::arg("mP") = 0, py::arg("qR") = 0);
+  m.def("mx4_prefix_select", [](int NQ, uptr T, uptr mP, uptr qR, uptr pbounds, uptr margin8,
+                                uptr probe_s, uptr probe_p, int n_cols, float rate, uptr tail_cs,
+                                uptr tail_cp, int tail_cap, float limit, uptr thrP, uptr nvp,
+                                uptr st, int ld, int tile_stride, int tail_ld, bool nvp_zeroed,
+                                float band) {
+    check(symb_mx4_prefix_select(NQ, P<const float>(T), P<const float>(mP), P<const float>(qR),
+                                 P<const float>(pbounds), P<const float>(margin8),
+                                 P<const float>(probe_s), P<const float>(probe_p), n_cols, ld,
+                                 tile_stride, rate, P<const float>(tail_cs),
+                                 P<const float>(tail_cp), tail_cap, tail_ld, limit, P<float>(thrP),
+                                 P<int>(nvp), S(st), nvp_zeroed ? 1 : 0, band),
+          "mx4_prefix_select");
+  }, py::arg("NQ"), py::arg("T"), py::arg("mP"), py::arg("qR"), py::arg("pbounds"),
+     py::arg("margin8"), py::arg("probe_s"), py::arg("probe_p"), py::arg("n_cols"),
+     py::arg("rate"), py::arg("tail_cs"), py::arg("tail_cp"), py::arg("tail_cap"),
+     py::arg("limit"), py::arg("thrP"), py::arg("nvp"), py::arg("stream"), py::arg("ld") = 0,
+     py::arg("tile_stride") = 1, py::arg("tail_ld") = 0, py::arg("nvp_zeroed") = false,
+     py::arg("band") = 1.0f);
   m.def("quant_rows_mx4", [](uptr X, int n, int dim, uptr X4, uptr SC, uptr bounds, uptr margin,
                              uptr st) {
     check(symb_quant_rows_mx4(P<void>(X), n, dim, P<void>(X4), P<void>(SC), P<float>(bounds),

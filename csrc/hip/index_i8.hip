@@ -1151,6 +1151,74 @@ __global__ __launch_bounds__(256) void mx4_select_kernel(
   }
 }
 
+// The prefix tier's choice (after mx4_select_kernel; index_stream.hip scan_stream_kernel NKP_).
+// The prefix scan emits the rows whose estimate over the first dims, q~_P . x~_P, reaches
+//   thrP = T - mP - qR XR        (mP = |q_P| E_P + |q_P - q~_P| X_P + 1e-5, qR = |q_R|,
+//                                 XR = pbounds[2] = max |x_R| over the rows):
+// a superset of the rows with q . x >= T, as q . x <= q~_P . x~_P + mP + |q_R| |x_R|.  Such a row's
+// exact partial score q_P . x_P is at least thrP - mP, so the tier's candidates beyond the per-block
+// route's are estimated as in mx4_select_kernel: probe rows (and tail rows) with exact score
+// < T - margin8 and partial score >= thrP - band mP.  band = 1 is the worst case; it needs the
+// image's error vectors to line up with the query, and on a 100M-row shard it counts the bulk's
+// 2-sigma tail where the scan emits nothing (profiles/prefix_tier/README.md), so the shard passes
+// a fraction (index/shard.py PREFIX_BAND).  The prefix tier is viable iff, for EVERY query,
+// thrP is finite and > 0 and probe count x rate + tail count <= limit; otherwise *nvp ends 1 (the
+// whole-row fp4 scan runs if mx4_select_kernel left its tier viable).  An estimate only: a
+// batch that emits more than it foresaw overflows into the exact fall-back.  probe_p / tail_cp:
+// the partial scores (dense_scores_kernel KP), laid out as probe_s / tail_cs.
+__global__ __launch_bounds__(256) void mx4_prefix_select_kernel(
+    int NQ, const float* __restrict__ T, const float* __restrict__ mP, const float* __restrict__ qR,
+    const float* __restrict__ pbounds, const float* __restrict__ margin8,
+    const float* __restrict__ probe_s, const float* __restrict__ probe_p, int n_cols, int ld,
+    int tile_stride, float rate, const float* __restrict__ tail_cs,
+    const float* __restrict__ tail_cp, int tail_cap, int tail_ld, float limit, float band,
+    float* __restrict__ thrP, int* __restrict__ nvp) {
+  __shared__ float red[2][4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int q = blockIdx.x;
+  const float t = T[q];
+  const float tp = t - mP[q] - qR[q] * pbounds[2];
+  const float lo = tp - band * mP[q], hi = t - margin8[q];
+  float c = 0.f;
+  const float* ps = probe_s + (size_t)q * ld;
+  const float* pp = probe_p + (size_t)q * ld;
+  const int n_probe = ((n_cols + 63) / 64 + tile_stride - 1) / tile_stride * 64;
+  auto pcol = [&](int j) { return ((j >> 6) * tile_stride << 6) + (j & 63); };
+  int j = threadIdx.x;
+  for (; j + 3 * 256 < n_probe; j += 4 * 256) {
+    float v[4], u4[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int col = pcol(j + u * 256);
+      v[u] = col < n_cols ? ps[col] : INFINITY;
+      u4[u] = col < n_cols ? pp[col] : -INFINITY;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) c += (u4[u] >= lo && v[u] < hi) ? 1.f : 0.f;
+  }
+  for (; j < n_probe; j += 256) {
+    const int col = pcol(j);
+    if (col < n_cols) c += (pp[col] >= lo && ps[col] < hi) ? 1.f : 0.f;
+  }
+  float tc = 0.f;
+  const float* tcs = tail_cs + (size_t)q * tail_ld;
+  const float* tcp = tail_cp + (size_t)q * tail_ld;
+  for (int i = threadIdx.x; i < tail_cap; i += 256) tc += (tcp[i] >= lo && tcs[i] < hi) ? 1.f : 0.f;
+  c = wave_sum(c);
+  tc = wave_sum(tc);
+  if (lane == 0) {
+    red[0][w] = c;
+    red[1][w] = tc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    c = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    tc = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    thrP[q] = tp;
+    if (!(tp > 0.f && tp < INFINITY && c * rate + tc <= limit)) atomicOr(nvp, 1);
+  }
+}
+
 constexpr int ROUTE_MAX_BLOCKS = 1024;   // int8 row blocks the per-block route can bin
 
 // The exact tail scan's candidates (rows >= thr0 of the fresh rows [off, n), ids relative to
@@ -1561,6 +1629,32 @@ int symb_mx4_select(int NQ, const float* T, const float* margin4, const float* m
   hipLaunchKernelGGL(mx4_select_kernel, dim3(NQ), dim3(256), 0, st, NQ, T, margin4, margin8,
                      probe_s, n_cols, ld, tile_stride, rate, tail_cs, tail_cap, tail_ld, limit,
                      thr4, nv);
+  return (int)hipGetLastError();
+}
+
+// The prefix tier's choice (mx4_prefix_select_kernel); *nvp is zeroed here unless nvp_zeroed.
+int symb_mx4_prefix_select(int NQ, const float* T, const float* mP, const float* qR,
+                           const float* pbounds, const float* margin8, const float* probe_s,
+                           const float* probe_p, int n_cols, int ld, int tile_stride, float rate,
+                           const float* tail_cs, const float* tail_cp, int tail_cap, int tail_ld,
+                           float limit, float* thrP, int* nvp, hipStream_t st, int nvp_zeroed,
+                           float band) {
+  if (NQ <= 0) return 0;
+  if (!(band >= 0.f && band <= 1.f)) return -1;
+  if (ld <= 0) ld = n_cols;
+  if (tail_ld <= 0) tail_ld = tail_cap;
+  if (n_cols <= 0 || ld < n_cols || tile_stride < 1 || tail_cap < 0 || tail_ld < tail_cap ||
+      probe_s == nullptr || probe_p == nullptr || T == nullptr || mP == nullptr ||
+      qR == nullptr || pbounds == nullptr || margin8 == nullptr || thrP == nullptr ||
+      nvp == nullptr || (tail_cap > 0 && (tail_cs == nullptr || tail_cp == nullptr)))
+    return -1;
+  if (!nvp_zeroed) {
+    hipError_t e = hipMemsetAsync(nvp, 0, sizeof(int), st);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(mx4_prefix_select_kernel, dim3(NQ), dim3(256), 0, st, NQ, T, mP, qR, pbounds,
+                     margin8, probe_s, probe_p, n_cols, ld, tile_stride, rate, tail_cs, tail_cp,
+                     tail_cap, tail_ld, limit, band, thrP, nvp);
   return (int)hipGetLastError();
 }
 

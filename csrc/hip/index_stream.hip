@@ -115,18 +115,33 @@ __device__ __forceinline__ float max16(const float (&v)[16]) {
 // once, so nothing is lost by not keeping it in L2 -- and the stream stops evicting what kernels
 // on other streams re-read from L2 (the encoder beside the scan).  Queries, centroids and
 // thresholds keep the default policy.
-template <int FMT, int D, int ABL = 0, int PACK = 1, int DEPTH_ = 0, bool NT_ = false>
-__global__ __launch_bounds__((64 * SGeo<FMT, D>::NW * PACK), 1) void scan_stream_kernel(
+// NKP_: the prefix form (MX-fp4, NW == 1, NT_): only k-steps 0 .. NKP_ - 1 of every sub-tile
+// record are read -- fragments ks < NKP_ and the scale dwords that hold their scales -- and the
+// estimate is the decoded dot over the first 64 NKP_ dims, q~_P . x~_P.  The image is the same;
+// the caller passes thresholds that bound the remainder (index/shard.py, the prefix tier).  The
+// centroid test stays valid on the prefix: |(q~ - c~)_P| <= |q~ - c~| <= R_s and |x~_P| <= X4.
+// 0 (or NKS): every k-step, the kernel as it was.  A CU-granular prefix workgroup asks for more
+// than half of a CU's LDS (launch_stream), since its waves no longer fill the register file.
+// G2_: a second gate word (gate2 / gate2_want, both must pass) and a second run counter (runs2);
+// the arguments are not read otherwise.
+template <int FMT, int D, int ABL = 0, int PACK = 1, int DEPTH_ = 0, bool NT_ = false,
+          int NKP_ = 0, bool G2_ = false>
+__device__ __forceinline__ void scan_stream_body(
     const uint8_t* __restrict__ img, int n_valid, int rows_per_blk, const uint8_t* __restrict__ Q,
     const uint32_t* __restrict__ qsc, int NQ, int n_qblk, int n_lb, int xcd,
     const float* __restrict__ thr_in,
     float* __restrict__ cand_s, int* __restrict__ cand_i, int* __restrict__ cand_n, int cap,
     const int* __restrict__ skip, const int* __restrict__ gate, int gate_want,
     int* __restrict__ runs, const uint8_t* __restrict__ cent4, const uint32_t* __restrict__ centqs,
-    const float* __restrict__ centR, const float* __restrict__ bounds4) {
+    const float* __restrict__ centR, const float* __restrict__ bounds4,
+    const int* __restrict__ gate2, int gate2_want, int* __restrict__ runs2) {
   using S = SDim<FMT, D>;
   using G = SGeo<FMT, D>;
-  constexpr int NKS = S::NKS, NSC = S::NSC ? S::NSC : 1, REC = S::REC;
+  constexpr bool PFX = NKP_ > 0 && NKP_ < S::NKS;
+  static_assert(!PFX || (FMT == SF_MX4 && G::NW == 1 && NT_ && ABL == 0), "the prefix form");
+  // k-steps and scale dwords in use (S::NKS, NSCR: the whole row's, the images' strides)
+  constexpr int NKS = PFX ? NKP_ : S::NKS, REC = S::REC;
+  constexpr int NSCR = S::NSC ? S::NSC : 1, NSC = PFX ? (NKP_ + 3) / 4 : NSCR;
   constexpr int SETS = G::SETS, DEPTH = DEPTH_ ? DEPTH_ : G::DEPTH, STW = G::STW;
   static_assert(PACK >= 1 && G::NW * PACK <= 4, "one wave per SIMD");
   static_assert(!NT_ || G::NW == 1, "non-temporal rows: a sub-tile must be read by one wave only");
@@ -139,6 +154,10 @@ __global__ __launch_bounds__((64 * SGeo<FMT, D>::NW * PACK), 1) void scan_stream
   const int lb = PACK == 1 ? wg : PACK * wg + wave_wg / G::NW;
   const int qb = lb % n_qblk, rb = lb / n_qblk;
   if (gate != nullptr && *gate != gate_want) return;   // (no barrier in this kernel)
+  if constexpr (G2_) {
+    if (gate2 != nullptr && *gate2 != gate2_want) return;
+    if (runs2 != nullptr && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(runs2, 1);
+  }
   // runs (optional): counts the launches that passed the gate (the MX-fp4 tier's batches)
   if (runs != nullptr && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(runs, 1);
   if constexpr (PACK > 1) {
@@ -167,7 +186,7 @@ __global__ __launch_bounds__((64 * SGeo<FMT, D>::NW * PACK), 1) void scan_stream
 #pragma unroll
     for (int j = 0; j < NSC; ++j) {
       if constexpr (FMT != SF_I8)
-        qs[s][j] = qsc[(size_t)qq * 2 * NSC + h * NSC + j];
+        qs[s][j] = qsc[(size_t)qq * 2 * NSCR + h * NSCR + j];
       else
         qs[s][j] = 0u;
     }
@@ -191,7 +210,7 @@ __global__ __launch_bounds__((64 * SGeo<FMT, D>::NW * PACK), 1) void scan_stream
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) cf[ks] = *reinterpret_cast<const i32x4s*>(cp + 32 * ks);
 #pragma unroll
-      for (int j = 0; j < NSC; ++j) cqs[j] = centqs[(size_t)gs * 2 * NSC + h * NSC + j];
+      for (int j = 0; j < NSC; ++j) cqs[j] = centqs[(size_t)gs * 2 * NSCR + h * NSCR + j];
       const float x4 = bounds4[1];
 #pragma unroll
       for (int s = 0; s < SETS; ++s) {
@@ -384,6 +403,48 @@ __global__ __launch_bounds__((64 * SGeo<FMT, D>::NW * PACK), 1) void scan_stream
   if (nst) flush();
 }
 
+template <int FMT, int D, int ABL = 0, int PACK = 1, int DEPTH_ = 0, bool NT_ = false,
+          int NKP_ = 0, bool G2_ = false>
+__global__ __launch_bounds__((64 * SGeo<FMT, D>::NW * PACK), 1) void scan_stream_kernel(
+    const uint8_t* __restrict__ img, int n_valid, int rows_per_blk, const uint8_t* __restrict__ Q,
+    const uint32_t* __restrict__ qsc, int NQ, int n_qblk, int n_lb, int xcd,
+    const float* __restrict__ thr_in,
+    float* __restrict__ cand_s, int* __restrict__ cand_i, int* __restrict__ cand_n, int cap,
+    const int* __restrict__ skip, const int* __restrict__ gate, int gate_want,
+    int* __restrict__ runs, const uint8_t* __restrict__ cent4, const uint32_t* __restrict__ centqs,
+    const float* __restrict__ centR, const float* __restrict__ bounds4,
+    const int* __restrict__ gate2, int gate2_want, int* __restrict__ runs2) {
+  scan_stream_body<FMT, D, ABL, PACK, DEPTH_, NT_, NKP_, G2_>(
+      img, n_valid, rows_per_blk, Q, qsc, NQ, n_qblk, n_lb, xcd, thr_in, cand_s, cand_i, cand_n, cap,
+      skip, gate, gate_want, runs, cent4, centqs, centR, bounds4, gate2, gate2_want, runs2);
+}
+
+// The MX-fp4 tier at dim 384 in ONE launch that picks its form on the device: *form == 0 runs
+// the prefix body (NKP_ k-steps, DEPTHP_ sub-tiles in flight, thresholds thr_p, the centroid
+// test's row bound from pbounds, runs2 counted), anything else the whole-row body (thr_in,
+// bounds4) -- so a search enqueues one fp4 launch, not one per form.  Both bodies are the
+// non-temporal ones.  The kernel's registers are the whole-row body's (occupancy 1), so the
+// CU-granular form keeps a CU to itself as that form does.
+template <int PACK, int DEPTHP_, int NKP_>
+__global__ __launch_bounds__((64 * SGeo<SF_MX4, 384>::NW * PACK), 1) void scan_stream_dual_kernel(
+    const uint8_t* __restrict__ img, int n_valid, int rows_per_blk, const uint8_t* __restrict__ Q,
+    const uint32_t* __restrict__ qsc, int NQ, int n_qblk, int n_lb, int xcd,
+    const float* __restrict__ thr_in, const float* __restrict__ thr_p,
+    float* __restrict__ cand_s, int* __restrict__ cand_i, int* __restrict__ cand_n, int cap,
+    const int* __restrict__ skip, const int* __restrict__ gate, int gate_want,
+    int* __restrict__ runs, const uint8_t* __restrict__ cent4, const uint32_t* __restrict__ centqs,
+    const float* __restrict__ centR, const float* __restrict__ bounds4,
+    const float* __restrict__ pbounds, const int* __restrict__ form, int* __restrict__ runs2) {
+  if (*form == 0)
+    scan_stream_body<SF_MX4, 384, 0, PACK, DEPTHP_, true, NKP_, true>(
+        img, n_valid, rows_per_blk, Q, qsc, NQ, n_qblk, n_lb, xcd, thr_p, cand_s, cand_i, cand_n,
+        cap, skip, gate, gate_want, runs, cent4, centqs, centR, pbounds, nullptr, 0, runs2);
+  else
+    scan_stream_body<SF_MX4, 384, 0, PACK, 0, true, 0, false>(
+        img, n_valid, rows_per_blk, Q, qsc, NQ, n_qblk, n_lb, xcd, thr_in, cand_s, cand_i, cand_n,
+        cap, skip, gate, gate_want, runs, cent4, centqs, centR, bounds4, nullptr, 0, nullptr);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Image writers.  Row r of sub-tile g = r >> 5, rr = r & 31; row byte b (k-step ks = b >> 5,
 // half hh = (b >> 4) & 1, byte bi = b & 15) sits at REC g + HDR + 1024 ks + 16 (32 hh + rr) + bi.
@@ -501,11 +562,17 @@ __device__ __forceinline__ int mx_block_exp(float amax, float top) {
 // Xq [.][D / 2] and the scale record QS [.][2 NSC] dwords (dword h NSC + j, byte b = block
 // 2 (4 j + b) + h: the scan's per-lane B scales).
 // en / nn / xn = |x - x~| / |x~| / |x|.
+// pn (nkp > 0): the same norms split at dim 64 nkp, for the prefix tier's bounds --
+// |x_P - x~_P|, |x~_P|, |x_P| over the first nkp k-steps and |x_R| over the rest.  (By reference
+// and never optional: a pointer that may be null kept the struct in scratch.)
+struct MxPrefixNorms {
+  float ep, np, xp, xr;
+};
 template <int D, bool QUERY>
 __device__ __forceinline__ void mx_stream_row(const __bf16* __restrict__ xrow, int row,
                                               uint8_t* __restrict__ img, uint8_t* __restrict__ Xq,
                                               uint32_t* __restrict__ QS, float& en, float& nn,
-                                              float& xn) {
+                                              float& xn, int nkp, MxPrefixNorms& pn) {
   using S = SDim<SF_MX4, D>;
   constexpr int M = D / 64, NSC = S::NSC;
   constexpr float TOP = 6.f;
@@ -517,6 +584,7 @@ __device__ __forceinline__ void mx_stream_row(const __bf16* __restrict__ xrow, i
 #pragma unroll
   for (int i = 0; i < NSC; ++i) scw[i] = 0u;
   float e2 = 0.f, n2 = 0.f, x2 = 0.f;
+  float e2p = 0.f, n2p = 0.f, x2p = 0.f, x2r = 0.f;   // (k-steps m < nkp; x2r: the others)
 #pragma unroll
   for (int m = 0; m < M; ++m) {
     const float x = __uint_as_float((uint32_t)xp[lane + 64 * m] << 16);
@@ -531,6 +599,13 @@ __device__ __forceinline__ void mx_stream_row(const __bf16* __restrict__ xrow, i
     e2 += (x - xt) * (x - xt);
     n2 += xt * xt;
     x2 += x * x;
+    if (nkp > 0) {
+      const bool inp = m < nkp;
+      e2p += inp ? (x - xt) * (x - xt) : 0.f;
+      n2p += inp ? xt * xt : 0.f;
+      x2p += inp ? x * x : 0.f;
+      x2r += inp ? 0.f : x * x;
+    }
     const int hi = __shfl_down(code, 1);
     const uint8_t byte = (uint8_t)(code | (hi << 4));
     const int bj = (lane >> 1) + 32 * m;     // row byte of the even lane's pair
@@ -548,6 +623,12 @@ __device__ __forceinline__ void mx_stream_row(const __bf16* __restrict__ xrow, i
   en = sqrtf(wave_sum(e2));
   nn = sqrtf(wave_sum(n2));
   xn = sqrtf(wave_sum(x2));
+  if (nkp > 0) {
+    pn.ep = sqrtf(wave_sum(e2p));
+    pn.np = sqrtf(wave_sum(n2p));
+    pn.xp = sqrtf(wave_sum(x2p));
+    pn.xr = sqrtf(wave_sum(x2r));
+  }
   if constexpr (query) {
     // lanes 0 and 32 built the two halves' scale words (identical within a half-wave)
 #pragma unroll
@@ -565,9 +646,9 @@ template <int D>
 __device__ __forceinline__ void mx4_stream_row(const __bf16* __restrict__ xrow, int row,
                                                uint8_t* __restrict__ img, uint8_t* __restrict__ Xq,
                                                uint32_t* __restrict__ QS, float& en, float& nn,
-                                               float& xn) {
-  if (Xq != nullptr) mx_stream_row<D, true>(xrow, row, img, Xq, QS, en, nn, xn);
-  else mx_stream_row<D, false>(xrow, row, img, Xq, QS, en, nn, xn);
+                                               float& xn, int nkp, MxPrefixNorms& pn) {
+  if (Xq != nullptr) mx_stream_row<D, true>(xrow, row, img, Xq, QS, en, nn, xn, nkp, pn);
+  else mx_stream_row<D, false>(xrow, row, img, Xq, QS, en, nn, xn, nkp, pn);
 }
 
 __device__ __forceinline__ float e2m1_value(int c) {   // 4-bit code (sign bit 3) -> value
@@ -690,6 +771,23 @@ __device__ __forceinline__ void raise_bounds2(float* bounds, float a, float b) {
   }
 }
 
+// raise pb[0..2] = (E_P, X_P, XR), the prefix tier's bounds, the same way
+__device__ __forceinline__ void raise_bounds3(float* pb, float a, float b, float c) {
+  __shared__ float red[3][4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[0][w] = a;
+    red[1][w] = b;
+    red[2][w] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const float m = fmaxf(fmaxf(red[threadIdx.x][0], red[threadIdx.x][1]),
+                          fmaxf(red[threadIdx.x][2], red[threadIdx.x][3]));
+    atomicMax(reinterpret_cast<int*>(pb) + threadIdx.x, __float_as_int(m));
+  }
+}
+
 // int8 stream image of whole sub-tiles of the bf16 rows X (i8_stream_tile): tiles g_lo +
 // blockIdx.x, or (rows != nullptr) the tile of listed row rows[blockIdx.x] -- a tile listed twice
 // is written twice with the same bytes; bounds (2 floats) raised to (max |x - x~|, max |x~|).
@@ -707,38 +805,54 @@ __global__ __launch_bounds__(512) void quant_stream_i8_kernel(const __bf16* __re
 // MX-fp4 stream image of bf16 rows (margin == nullptr: rows [r0, r0 + n) or the listed
 // rows into img, bounds[0..1] raised to (E, X)) or the query image (margin != nullptr: Xq / QS for
 // rows 0 .. n - 1 and margin = |q| E + |q - q~| X + 1e-5 from bounds).  One wave per row.
+// pbounds (optional, with nkp = the prefix k-steps): rows raise pbounds[0..2] to (E_P, X_P, XR) =
+// max (|x_P - x~_P|, |x~_P|, |x_R|); queries write mP = |q_P| E_P + |q_P - q~_P| X_P + 1e-5 and
+// qR = |q_R| from them.
 template <int D>
 __global__ __launch_bounds__(256) void quant_stream_mx4_kernel(
     const __bf16* __restrict__ X, int r0, const int* __restrict__ rows, int n,
     uint8_t* __restrict__ img, uint8_t* __restrict__ Xq, uint32_t* __restrict__ QS,
-    float* __restrict__ bounds, float* __restrict__ margin) {
+    float* __restrict__ bounds, float* __restrict__ margin, float* __restrict__ pbounds, int nkp,
+    float* __restrict__ mP, float* __restrict__ qR) {
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
   const bool query = margin != nullptr;
   float en = 0.f, nn = 0.f, xn = 0.f;
+  MxPrefixNorms pn{0.f, 0.f, 0.f, 0.f};
+  if (pbounds == nullptr) nkp = 0;
   if (query) {
     if (j >= n) return;   // (no barrier on the query path)
-    mx_stream_row<D, true>(X + (size_t)j * D, j, nullptr, Xq, QS, en, nn, xn);
-    if ((threadIdx.x & 63) == 0) margin[j] = xn * bounds[0] + en * bounds[1] + 1e-5f;
+    mx_stream_row<D, true>(X + (size_t)j * D, j, nullptr, Xq, QS, en, nn, xn, nkp, pn);
+    if ((threadIdx.x & 63) == 0) {
+      margin[j] = xn * bounds[0] + en * bounds[1] + 1e-5f;
+      if (pbounds != nullptr) {
+        mP[j] = pn.xp * pbounds[0] + pn.ep * pbounds[1] + 1e-5f;
+        qR[j] = pn.xr;
+      }
+    }
     return;
   }
   if (j < n) {
     const int row = rows ? rows[j] : r0 + j;
-    mx_stream_row<D, false>(X + (size_t)row * D, row, img, nullptr, nullptr, en, nn, xn);
+    mx_stream_row<D, false>(X + (size_t)row * D, row, img, nullptr, nullptr, en, nn, xn, nkp, pn);
   }
   raise_bounds2(bounds, en, nn);
+  if (pbounds != nullptr) raise_bounds3(pbounds, pn.ep, pn.np, pn.xr);
 }
 
 // An append of n unit bf16 rows at row r0: the rows themselves (src -> rows) and their MX-fp4
-// stream image (img4, bounds b4[0..1]; may be absent, nullptr).  One wave per row.  (The int8
+// stream image (img4, bounds b4[0..1]; may be absent, nullptr; pb4 (optional): the prefix tier's
+// bounds over the first nkp k-steps).  One wave per row.  (The int8
 // image's sub-tiles follow in a second launch: their shared scale needs every row of the tile
 // written first.)
 template <int D>
 __global__ __launch_bounds__(256) void append_rows_kernel(const __bf16* __restrict__ src, int n,
                                                           __bf16* __restrict__ rows, int r0,
                                                           uint8_t* __restrict__ img4,
-                                                          float* __restrict__ b4) {
+                                                          float* __restrict__ b4,
+                                                          float* __restrict__ pb4, int nkp) {
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   float e4 = 0.f, n4 = 0.f, x4 = 0.f;
+  MxPrefixNorms pn{0.f, 0.f, 0.f, 0.f};
   if (j < n) {
     const __bf16* xr = src + (size_t)j * D;
     // the bf16 row: D * 2 bytes as 4-byte words, D / 128 per lane
@@ -746,9 +860,11 @@ __global__ __launch_bounds__(256) void append_rows_kernel(const __bf16* __restri
     uint32_t* dp = reinterpret_cast<uint32_t*>(rows + (size_t)(r0 + j) * D);
 #pragma unroll
     for (int i = 0; i < D / 128; ++i) dp[lane + 64 * i] = sp[lane + 64 * i];
-    if (img4) mx4_stream_row<D>(xr, r0 + j, img4, nullptr, nullptr, e4, n4, x4);
+    if (img4) mx4_stream_row<D>(xr, r0 + j, img4, nullptr, nullptr, e4, n4, x4,
+                                pb4 != nullptr ? nkp : 0, pn);
   }
   if (b4) raise_bounds2(b4, e4, n4);
+  if (pb4) raise_bounds3(pb4, pn.ep, pn.np, pn.xr);   // (E_P, X_P, XR: quant_stream_mx4_kernel)
 }
 
 // Probe of one v_mfma_scale_f32_32x32x64_f8f6f4 (tests: the operand bit layouts of the f8f6f4
@@ -842,21 +958,58 @@ struct CentArgs {   // the MX-fp4 centroid test's inputs (all nullptr: off)
 
 // WIDE: the CU-granular form (PACK = 4 / NW thin workgroups per workgroup; a 4-wave thin form is
 // its own CU-granular form); DEPTH_: sub-tiles in flight (0: SGeo's); NT_: non-temporal row loads
-template <int F, int D, int ABL = 0, bool WIDE = false, int DEPTH_ = 0, bool NT_ = false>
+struct Gate2Args {   // the second gate word and run counter (scan_stream_kernel G2_; nullptr: off)
+  const int* gate;
+  int want;
+  int* runs;
+};
+
+// LDS a CU-granular prefix workgroup asks for: more than half of a CU's 160 KiB, so that a CU
+// holds one such workgroup whatever registers its waves use
+constexpr int PREFIX_WIDE_LDS = 81 * 1024;
+
+template <int F, int D, int ABL = 0, bool WIDE = false, int DEPTH_ = 0, bool NT_ = false,
+          int NKP_ = 0, bool G2_ = false>
 static int launch_stream(const void* img, int n_valid, int rows_per_blk, int n_rblk, const void* Q,
                          const void* qsc, int NQ, const float* thr, float* cand_s, int* cand_i,
                          int* cand_n, int cap, int xcd, hipStream_t st, const int* skip,
-                         const int* gate, int gate_want, int* runs, CentArgs ca) {
+                         const int* gate, int gate_want, int* runs, CentArgs ca,
+                         Gate2Args g2 = {nullptr, 0, nullptr}) {
   using G = SGeo<F, D>;
   constexpr int PACK = WIDE ? 4 / G::NW : 1;
   const int n_qblk = (NQ + G::QPB - 1) / G::QPB, n_lb = n_rblk * n_qblk;
-  constexpr int lds = G::STAGE * G::NW * PACK;
-  if (lds > 64 * 1024) set_max_lds<scan_stream_kernel<F, D, ABL, PACK, DEPTH_, NT_>>(lds);
-  hipLaunchKernelGGL((scan_stream_kernel<F, D, ABL, PACK, DEPTH_, NT_>), dim3((n_lb + PACK - 1) / PACK),
+  constexpr bool PFX = NKP_ > 0 && NKP_ < SDim<F, D>::NKS;
+  constexpr int lds = WIDE && PFX ? PREFIX_WIDE_LDS : G::STAGE * G::NW * PACK;
+  static_assert(lds >= G::STAGE * G::NW * PACK, "the waves' candidate stages");
+  if (lds > 64 * 1024)
+    set_max_lds<scan_stream_kernel<F, D, ABL, PACK, DEPTH_, NT_, NKP_, G2_>>(lds);
+  hipLaunchKernelGGL((scan_stream_kernel<F, D, ABL, PACK, DEPTH_, NT_, NKP_, G2_>),
+                     dim3((n_lb + PACK - 1) / PACK),
                      dim3(64 * G::NW * PACK), lds, st, (const uint8_t*)img, n_valid, rows_per_blk,
                      (const uint8_t*)Q, (const uint32_t*)qsc, NQ, n_qblk, n_lb, xcd, thr, cand_s,
                      cand_i, cand_n, cap, skip, gate, gate_want, runs, (const uint8_t*)ca.c4,
-                     (const uint32_t*)ca.cqs, ca.R, ca.b4);
+                     (const uint32_t*)ca.cqs, ca.R, ca.b4, g2.gate, g2.want, g2.runs);
+  return (int)hipGetLastError();
+}
+
+template <bool WIDE, int DEPTHP_, int NKP_>
+static int launch_stream_dual(const void* img, int n_valid, int rows_per_blk, int n_rblk,
+                              const void* Q, const void* qsc, int NQ, const float* thr,
+                              const float* thr_p, float* cand_s, int* cand_i, int* cand_n, int cap,
+                              int xcd, hipStream_t st, const int* skip, const int* gate,
+                              int gate_want, int* runs, CentArgs ca, const float* pbounds,
+                              const int* form, int* runs2) {
+  using G = SGeo<SF_MX4, 384>;
+  constexpr int PACK = WIDE ? 4 / G::NW : 1;
+  const int n_qblk = (NQ + G::QPB - 1) / G::QPB, n_lb = n_rblk * n_qblk;
+  constexpr int lds = G::STAGE * G::NW * PACK;
+  static_assert(lds <= 64 * 1024, "the waves' candidate stages");
+  hipLaunchKernelGGL((scan_stream_dual_kernel<PACK, DEPTHP_, NKP_>), dim3((n_lb + PACK - 1) / PACK),
+                     dim3(64 * G::NW * PACK), lds, st, (const uint8_t*)img, n_valid, rows_per_blk,
+                     (const uint8_t*)Q, (const uint32_t*)qsc, NQ, n_qblk, n_lb, xcd, thr, thr_p,
+                     cand_s, cand_i, cand_n, cap, skip, gate, gate_want, runs,
+                     (const uint8_t*)ca.c4, (const uint32_t*)ca.cqs, ca.R, ca.b4, pbounds, form,
+                     runs2);
   return (int)hipGetLastError();
 }
 
@@ -870,22 +1023,46 @@ static int launch_stream(const void* img, int n_valid, int rows_per_blk, int n_r
 // in flight per wave, 0 = the form's default; 4 and 5 exist for MX-fp4 at dim 384.  nt: the
 // non-temporal row stream (scan_stream_kernel NT_), which exists for MX-fp4 at dim 384 at the
 // default depth only -- the one form whose sub-tiles are each read by a single wave.
+// prefix: 0, or the k-steps the prefix form reads (scan_stream_kernel NKP_: 2 or 3), which exists
+// for MX-fp4 at dim 384 with nt, at depth 0 / 3 and at the deep depth that keeps the bytes in
+// flight of the whole-row form (symb_stream_prefix_depth: 6 at prefix 3, 8 at prefix 2).
+// gate2 / gate2_want / runs2: a second gate word that must pass too, and a second counter of
+// launches that ran; only for the prefix forms.
+// thr_prefix != nullptr: the fp4 tier in one launch that picks its form on the device
+// (scan_stream_dual_kernel): *gate2 == 0 runs the prefix form (thresholds thr_prefix, `prefix`
+// k-steps at its deep depth, the centroid test's row bound pbounds[1], runs2 counted), any other
+// value the whole-row form (thr, bounds4) at the default depth.  gate2 is then required,
+// gate2_want unused, and pbounds required with the centroid test.
+int symb_stream_prefix_depth(int prefix) { return prefix == 3 ? 6 : prefix == 2 ? 8 : 0; }
+
 int symb_index_scan_stream(const void* img, int n_valid, int alloc_rows, int rows_per_blk,
                            int n_rblk, const void* Q, const void* qsc, int NQ, const float* thr,
                            float* cand_s, int* cand_i, int* cand_n, int cap, int xcd,
                            hipStream_t st, const int* skip, int dim, int form, const int* gate,
                            int gate_want, int zero_cnt, int* runs, const void* cent4,
                            const void* centqs, const float* centR, const float* bounds4, int wide,
-                           int depth, int nt) {
+                           int depth, int nt, int prefix, const int* gate2, int gate2_want,
+                           int* runs2, const float* thr_prefix, const float* pbounds) {
   if (NQ <= 0) return 0;
   if (wide < 0 || wide > 1 || nt < 0 || nt > 1) return -1;
+  if (prefix != 0 && prefix != 2 && prefix != 3) return -1;
+  if (prefix && !(form == 1 && dim == 384 && nt)) return -1;
+  if ((gate2 != nullptr || runs2 != nullptr) && !prefix) return -1;
+  if (thr_prefix != nullptr &&
+      (!prefix || gate2 == nullptr || depth != symb_stream_prefix_depth(prefix) ||
+       (cent4 != nullptr && pbounds == nullptr)))
+    return -1;
   static_assert(SGeo<SF_MX4, 384>::NW == 1, "the non-temporal form reads each sub-tile once");
   if (nt && !(form == 1 && dim == 384)) return -1;
   if (depth == SGeo<SF_MX4, 384>::DEPTH && form == 1 && dim == 384) depth = 0;
-  if (depth != 0 && !(form == 1 && dim == 384 && (depth == 4 || depth == 5))) return -1;
+  if (prefix) {
+    if (depth != 0 && depth != symb_stream_prefix_depth(prefix)) return -1;
+  } else if (depth != 0 && !(form == 1 && dim == 384 && (depth == 4 || depth == 5))) {
+    return -1;
+  }
   // (the ablations exist in the thin form at the default depth)
   if ((depth != 0 || wide || nt) && g_stream_abl != 0) return -1;
-  if (nt && depth != 0) return -1;
+  if (nt && depth != 0 && !prefix) return -1;
   if (cent4 != nullptr && (form != 1 || centqs == nullptr || centR == nullptr || bounds4 == nullptr))
     return -1;
   const CentArgs ca{cent4, centqs, centR, bounds4};
@@ -906,6 +1083,26 @@ int symb_index_scan_stream(const void* img, int n_valid, int alloc_rows, int row
   (g_stream_abl == 1   ? L(F, D_, 1, false, 0)    \
    : g_stream_abl == 2 ? L(F, D_, 2, false, 0)    \
                        : LW(F, D_, 0))
+  const Gate2Args g2{gate2, gate2_want, runs2};
+#define LP(W_, DP_, K_)                                                                          \
+  launch_stream<SF_MX4, 384, 0, W_, DP_, true, K_, true>(img, n_valid, rows_per_blk, n_rblk, Q,  \
+                                                         qsc, NQ, thr, cand_s, cand_i, cand_n,   \
+                                                         cap, xcd, st, skip, gate, gate_want,    \
+                                                         runs, ca, g2)
+#define LDU(W_, DP_, K_)                                                                        \
+  launch_stream_dual<W_, DP_, K_>(img, n_valid, rows_per_blk, n_rblk, Q, qsc, NQ, thr, thr_prefix, \
+                                  cand_s, cand_i, cand_n, cap, xcd, st, skip, gate, gate_want,    \
+                                  runs, ca, pbounds, gate2, runs2)
+  if (thr_prefix != nullptr) {
+    if (prefix == 3) return wide ? LDU(true, 6, 3) : LDU(false, 6, 3);
+    return wide ? LDU(true, 8, 2) : LDU(false, 8, 2);
+  }
+#undef LDU
+  if (prefix == 3)
+    return depth ? (wide ? LP(true, 6, 3) : LP(false, 6, 3)) : (wide ? LP(true, 0, 3) : LP(false, 0, 3));
+  if (prefix == 2)
+    return depth ? (wide ? LP(true, 8, 2) : LP(false, 8, 2)) : (wide ? LP(true, 0, 2) : LP(false, 0, 2));
+#undef LP
   if (nt)
     return wide ? (launch_stream<SF_MX4, 384, 0, true, 0, true>(
                       img, n_valid, rows_per_blk, n_rblk, Q, qsc, NQ, thr, cand_s, cand_i, cand_n,
@@ -946,11 +1143,13 @@ int symb_quant_stream_i8(const void* X, int r0, const int* rows, int n, int dim,
                          float* bounds, hipStream_t st);
 
 int symb_append_rows(const void* src, int n, int dim, void* rows, int r0, void* img8, float* b8,
-                     void* img4, float* b4, hipStream_t st) {
+                     void* img4, float* b4, hipStream_t st, float* pb4, int nkp) {
   if (n <= 0) return 0;
   if (r0 < 0 || rows == nullptr || src == nullptr || (img8 && !b8) || (img4 && !b4)) return -1;
+  if (pb4 && (!img4 || nkp < 1 || nkp > dim / 64)) return -1;
 #define L(D_) hipLaunchKernelGGL(append_rows_kernel<D_>, dim3((n + 3) / 4), dim3(256), 0, st,       \
-                                 (const __bf16*)src, n, (__bf16*)rows, r0, (uint8_t*)img4, b4)
+                                 (const __bf16*)src, n, (__bf16*)rows, r0, (uint8_t*)img4, b4, pb4,  \
+                                 nkp)
   if (dim == 384) L(384);
   else if (dim == 768) L(768);
   else if (dim == 1024) L(1024);
@@ -980,15 +1179,19 @@ int symb_quant_stream_i8(const void* X, int r0, const int* rows, int n, int dim,
 // MX-fp4 stream image of bf16 rows (margin == nullptr: rows [r0, r0 + n) or the listed rows into
 // img, bounds raised) or the query image (margin != nullptr: Xq / QS / margin for rows 0 .. n-1).
 int symb_quant_stream_mx4(const void* X, int r0, const int* rows, int n, int dim, void* img,
-                          void* Xq, void* QS, float* bounds, float* margin, hipStream_t st) {
+                          void* Xq, void* QS, float* bounds, float* margin, hipStream_t st,
+                          float* pbounds, int nkp, float* mP, float* qR) {
   if (n <= 0) return 0;
   if (bounds == nullptr) return -1;
+  if (pbounds != nullptr && (nkp < 1 || nkp > dim / 64)) return -1;
+  if (pbounds != nullptr && margin != nullptr && (mP == nullptr || qR == nullptr)) return -1;
+  if (pbounds == nullptr && (mP != nullptr || qR != nullptr)) return -1;
   if (margin == nullptr ? (img == nullptr || (rows == nullptr && r0 < 0))
                         : (Xq == nullptr || QS == nullptr))
     return -1;
 #define L(D_) hipLaunchKernelGGL(quant_stream_mx4_kernel<D_>, dim3((n + 3) / 4), dim3(256), 0, st,  \
                                  (const __bf16*)X, r0, rows, n, (uint8_t*)img, (uint8_t*)Xq,         \
-                                 (uint32_t*)QS, bounds, margin)
+                                 (uint32_t*)QS, bounds, margin, pbounds, nkp, mP, qR)
   if (dim == 384) L(384);
   else if (dim == 768) L(768);
   else if (dim == 1024) L(1024);

@@ -23,12 +23,16 @@ namespace symb {
 // by side over the queries: 32 TPW rows x 256 queries per workgroup, grid (row tiles / TPW,
 // query blocks).  TPW > 1 (D = 384): the wave's 64 query fragments stay in registers (192
 // VGPRs) across its TPW row tiles instead of being re-read from L2 for every 32 rows.
-template <int D, int TPW>
+// KP > 0: outp (same layout as out) also receives each score's partial sum over the first 16 KP
+// dims -- the accumulators as they stand after k-step KP - 1 (the prefix tier's choice,
+// index_i8.hip mx4_prefix_select_kernel); outp is not read with KP == 0.
+template <int D, int TPW, int KP = 0>
 __global__ __launch_bounds__(256) void dense_scores_kernel(const __bf16* __restrict__ X,
                                                            const int* __restrict__ rows, int n_list,
                                                            int ts, int div, int r_lo, int n_range,
                                                            const __bf16* __restrict__ Q, int NQ,
-                                                           float* __restrict__ out, int ld) {
+                                                           float* __restrict__ out, int ld,
+                                                           float* __restrict__ outp) {
   constexpr int KS = D / 16;
   constexpr bool RES = TPW > 1;   // resident query fragments
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
@@ -61,6 +65,28 @@ __global__ __launch_bounds__(256) void dense_scores_kernel(const __bf16* __restr
     }
     const __bf16* xp = X + (size_t)row * D + 8 * h;
     f32x16 acc0 = {}, acc1 = {};
+    // accumulator: col = query lane & 31, rows (r & 3) + 8 (r >> 2) + 4 h of the tile
+    auto store = [&](float* __restrict__ o) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int q = q0 + 32 * s + (lane & 31);
+        if (q >= NQ) continue;
+        float* op = o + (size_t)q * ld + j0 + 4 * h;
+        const f32x16& acc = s ? acc1 : acc0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int jj = j0 + 8 * c + 4 * h;
+          if (jj + 3 < m && (ld & 3) == 0) {
+            *reinterpret_cast<f32x4*>(op + 8 * c) =
+                f32x4{acc[4 * c], acc[4 * c + 1], acc[4 * c + 2], acc[4 * c + 3]};
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (jj + r < m) op[8 * c + r] = acc[4 * c + r];
+          }
+        }
+      }
+    };
     // (fully unrolled with resident fragments: a partially unrolled loop indexes rb0 / rb1
     // dynamically and the compiler puts them in scratch)
 #pragma unroll (RES ? KS : 8)
@@ -76,27 +102,11 @@ __global__ __launch_bounds__(256) void dense_scores_kernel(const __bf16* __restr
       }
       acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b0, acc0, 0, 0, 0);
       acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b1, acc1, 0, 0, 0);
-    }
-    // accumulator: col = query lane & 31, rows (r & 3) + 8 (r >> 2) + 4 h of the tile
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int q = q0 + 32 * s + (lane & 31);
-      if (q >= NQ) continue;
-      float* op = out + (size_t)q * ld + j0 + 4 * h;
-      const f32x16& acc = s ? acc1 : acc0;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int jj = j0 + 8 * c + 4 * h;
-        if (jj + 3 < m && (ld & 3) == 0) {
-          *reinterpret_cast<f32x4*>(op + 8 * c) =
-              f32x4{acc[4 * c], acc[4 * c + 1], acc[4 * c + 2], acc[4 * c + 3]};
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (jj + r < m) op[8 * c + r] = acc[4 * c + r];
-        }
+      if constexpr (KP > 0) {
+        if (ks == KP - 1) store(outp);
       }
     }
+    store(out);
   }
 }
 
@@ -138,18 +148,28 @@ int symb_prefill_candidates(int NQ, int r_lo, int n, int* cand_i, int* cand_n, i
 // rows == nullptr with n_list > 0: the hashed seed-tile list of (ts, div) (n_list a multiple of 64).
 int symb_dense_scores(const void* X, int dim, const int* rows, int n_list, int ts, int div,
                       int r_lo, int n_range, const void* Q, int NQ, float* out, int ld,
-                      hipStream_t st) {
+                      hipStream_t st, float* outp, int prefix_dims) {
   const int m = n_list + n_range;
   if (NQ <= 0 || m <= 0) return 0;
+  // (the partial scores exist at width 384 for the prefix tier's lengths: 128 or 192 dims)
+  if ((outp != nullptr) != (prefix_dims != 0)) return -1;
+  if (outp != nullptr && !(dim == 384 && (prefix_dims == 128 || prefix_dims == 192))) return -1;
   if (n_list < 0 || n_range < 0 || ld < m || r_lo < 0) return -1;
   if (n_list > 0 && rows == nullptr && (ts < 1 || ts > 24 || div < 1 || n_list % 64)) return -1;
 #define L(D_, T_) hipLaunchKernelGGL((dense_scores_kernel<D_, T_>), dim3((m + 32 * T_ - 1) / (32 * T_), (NQ + 255) / 256), \
                                      dim3(256), 0, st, (const __bf16*)X, rows, n_list, ts, div, r_lo, \
-                                     n_range, (const __bf16*)Q, NQ, out, ld)
-  if (dim == 384) L(384, SYMB_DS_TPW);
+                                     n_range, (const __bf16*)Q, NQ, out, ld, outp)
+#define LP(K_) hipLaunchKernelGGL((dense_scores_kernel<384, SYMB_DS_TPW, K_>),                        \
+                                  dim3((m + 32 * SYMB_DS_TPW - 1) / (32 * SYMB_DS_TPW), (NQ + 255) / 256), \
+                                  dim3(256), 0, st, (const __bf16*)X, rows, n_list, ts, div, r_lo,   \
+                                  n_range, (const __bf16*)Q, NQ, out, ld, outp)
+  if (prefix_dims == 128) LP(8);
+  else if (prefix_dims == 192) LP(12);
+  else if (dim == 384) L(384, SYMB_DS_TPW);
   else if (dim == 768) L(768, 1);
   else if (dim == 1024) L(1024, 1);
   else return -1;
+#undef LP
 #undef L
   return (int)hipGetLastError();
 }
